@@ -203,6 +203,36 @@ def cpu_baseline(size=128, ncls=3):
 
 METRIC = "3D-voxels/sec fwd+bwd, VNet 128^3 fp32"
 
+DUMP_BYTES = 60 * 10 ** 6     # --dump-outputs: every array together (plus the .npy headers) stays under 64 MB
+DUMP_STATE_ELEMS = 1 << 21    # values kept of the flattened parameters + BatchNorm buffers (~46 M at the default size)
+
+
+def sample_flat(a, k, seed=0):
+    """`a` itself when it has at most k elements, else k of its elements at fixed, seeded positions (flattened, in index order)."""
+    if a.size <= k:
+        return a
+    idx = np.sort(np.random.default_rng(seed).integers(0, a.size, k))
+    return np.ascontiguousarray(a).ravel()[idx]
+
+
+def dump_outputs(out_dir, model, logits_list, loss_list, per, loss):
+    """Write what one training step handed its caller to out_dir/<name>.npy: the loss (float64), its weighted terms, the per-class
+    dice, the logits (NCDHW float32) and the parameters + BatchNorm buffers after the update (state_dict order, flattened).
+    Arrays too large for DUMP_BYTES are stored as fixed, seeded samples.  Returns {name: [elements stored, elements in all]}."""
+    arrays = {"loss": np.array([float(loss)], np.float64),
+              "loss_terms": np.array([float(t) for t in loss_list], np.float64),
+              "per_channel_dice": np.asarray(per, np.float64)}
+    state = np.concatenate([v.ravel() for v in model.state_dict().values()])
+    arrays["state"] = sample_flat(state, DUMP_STATE_ELEMS)
+    (logits,) = logits_list   # VNet has one output
+    logits = logits.numpy()
+    arrays["logits"] = sample_flat(logits, (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // 4)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    sizes = {"state": state.size, "logits": logits.size}
+    return {name: [int(a.size), int(sizes.get(name, a.size))] for name, a in arrays.items()}
+
 
 def fallback_plans(args):
     """What `bench.py --gpus N` tries, in order, when an attempt fails or hangs (launch.run_supervised): the arrangement as
@@ -316,7 +346,13 @@ def main():
                     help="skip the untimed extra pass behind roofline.strict_fp32 (the step with exact bf16 x 3 operand pieces)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT",
                     help="msk_set_option knob for experiments, e.g. --opt wgrad_async=0 (not for the headline run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (loss, loss terms, per-class dice, logits, "
+                         "parameters + BatchNorm buffers after the update; fixed seeded samples keep it under 64 MB); the inputs "
+                         "are seeded, so two builds run with the same arguments can be compared array by array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and os.environ.get("MSEGK_SUPERVISED") != "1":
         raise SystemExit(supervised_main(args))
     worker_main(args)
@@ -369,6 +405,8 @@ def worker_main(args):
     eager = args.eager_opt if args.eager_opt is not None else (1 if (world == 1 and not args.force_syncbn_collectives) else 0)
     eager = bool(eager) and opt.enable_eager(model)
 
+    last_outputs = []   # what the latest step returned to its caller (--dump-outputs)
+
     def step():
         logits_list = net(images)
         loss_list, per = loss_computation(logits_list, labels, losses)
@@ -377,6 +415,7 @@ def worker_main(args):
         opt.step()
         sched.step()
         model.clear_gradients()
+        last_outputs[:] = (logits_list, loss_list, per, loss)
         return loss
 
     if args.no_sync_bn:
@@ -432,6 +471,8 @@ def worker_main(args):
             step_ms.append(float(ms.value))
     prof = dev.prof_report()
     loss_val = float(last)
+    # read back before the untimed extra passes below train the model further
+    dumped = dump_outputs(args.dump_outputs, model, *last_outputs) if args.dump_outputs and rank == 0 else None
     # untimed extra pass with the weight gradients on the MAIN stream: inside the timed region the data-gradient
     # launches of the dominant kernel share the GPU with the weight-gradient stream, which stretches their
     # HIP-event time; this pass gives the kernel's own duration (reported as roofline.serialized, not as value)
@@ -688,6 +729,8 @@ def worker_main(args):
            "roofline": roofline}
     if dp_info is not None:
         out["dp"] = dp_info
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "elements_stored_of_total": dumped}
     if args.profile_out:
         os.makedirs(os.path.dirname(os.path.abspath(args.profile_out)) or ".", exist_ok=True)
         with open(args.profile_out, "w") as f:

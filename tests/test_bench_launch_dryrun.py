@@ -99,3 +99,38 @@ def test_bench_single_process_defaults(tmp_path):
     bad = subprocess.run([sys.executable, os.path.join(HERE, "run_bench_fake.py"), "--gpus", "2", "--size", "16"],
                          env=env2, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float .npy files under 64 MB in all, the same on every run with the same
+    arguments; --steps is the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+    env = dict(os.environ, MSK_FAKE_LIB=_fake_lib(tmp_path), OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(HERE, "run_bench_fake.py"), "--steps", "3", "--warmup", "1",
+                              "--size", "16", "--no-cpu-baseline", "--dump-outputs", str(d)], env=env, cwd=ROOT,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert len(out.stdout.strip().splitlines()) == 1, out.stdout[:500]
+        rec = json.loads(out.stdout)
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert rec["roofline"]["event_steps"] == 1 and "3 timed steps" in rec["roofline"]["events"]   # every 4th of 3 steps
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in rec["dump_outputs"]["elements_stored_of_total"])
+        assert {"loss.npy", "loss_terms.npy", "per_channel_dice.npy", "logits.npy", "state.npy"} <= set(files)
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["logits.npy"].shape == (2, 3, 16, 16, 16)                            # small enough to be stored whole
+        stored, total = rec["dump_outputs"]["elements_stored_of_total"]["state"]
+        assert stored == arrays["state.npy"].size < total and np.abs(arrays["state.npy"]).max() > 0   # a seeded sample
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f
+    bad = subprocess.run([sys.executable, os.path.join(HERE, "run_bench_fake.py"), "--steps", "0", "--size", "16"],
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert bad.returncode != 0
