@@ -436,6 +436,18 @@ int msk_loss_bwd_ex(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, cons
                     int ignore_index, int dice_softmax, const float* dice_weight, const double* stats,
                     float coef_ce, float coef_dice, msk_tensor dlogits);
 
+/* BCELoss (losses/binary_cross_entropy_loss.py:84-172): binary_cross_entropy_with_logits against y = the label value
+ * (C == 1) or one_hot(label, C) (C > 1; a label outside [0, C) gives an all-zero row), masked by label != ignore_index,
+ * loss = mean(l * mask) / (mean(mask) + 1e-10) with mask [N,1,D,H,W].  weight_mode 0 = None, 1 = 'dynamic' (:131-139);
+ * pos_weight_mode 0 = None, 1 = pos_weight, 2 = 'dynamic' (:142-148).  The pos / neg / mask counts are exact.
+ * out[0] = loss; stats (device, 8 doubles) = {w_pos, w_neg, pw, scale, sum(l mask), sum(mask), pos, neg} for bwd. */
+int msk_bce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, int weight_mode,
+                int pos_weight_mode, float pos_weight, float* out, double* stats);
+/* dlogits (+)= coef * dloss/dlogits (accumulate != 0 adds: BCE after CE / Dice on the same logits); the weights
+ * carry no gradient (:161-162 stop_gradient) */
+int msk_bce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const double* stats,
+                float coef, int accumulate, msk_tensor dlogits);
+
 /* ---- optimizer --------------------------------------------------------------- */
 /* paddle.optimizer.Momentum(momentum, weight_decay=L2) over one flat arena
  * (cvlibs/config.py:212-214): g += wd*p; v = mu*v + g; p -= lr*v.

@@ -17,6 +17,7 @@ import numpy as np
 
 from ..datasets import DataLoader
 from ..device import to_tensor
+from ..models.losses.fused import TERM_SLOT
 from ..optimizer import lr as lr_mod
 from ..parallel import DataParallel, ParallelEnv, init_parallel_env
 from ..utils import TimeAverager, calculate_eta, logger, loss_computation, resume, save, train_profiler
@@ -176,7 +177,7 @@ def _snapshot(dev, loss, loss_list, per_channel_dice):
     """Keep the device scalars of one iteration alive past the next arena reset: the (2 + C)-float record
     {CE, dice loss, per-class dice} of EVERY distinct loss node (one per model output: VNetDeepSup has four) is copied
     into a small persistent ring (async d2d, no sync).  Returns (slots, terms, dsc_slot): terms = [(coef, slot index,
-    0 = CE | 1 = dice) per entry of loss_list], dsc_slot = the node per_channel_dice was taken from (the reference
+    0 = CE or BCE | 1 = dice) per entry of loss_list], dsc_slot = the node per_channel_dice was taken from (the reference
     reports the per-class dice of the LAST dice-bearing loss, utils/loss_utils.py:41-42)."""
     nodes, index = [], {}
     for l in loss_list:
@@ -191,7 +192,7 @@ def _snapshot(dev, loss, loss_list, per_channel_dice):
         ptr = _ring_slot(dev, n)
         dev.d2d(ptr, node.out_ptr, n * 4)
         slots.append((ptr, node.C))
-    terms = [[(c, index[id(node)], 0 if w == "ce" else 1) for c, node, w in l.terms] for l in loss_list]
+    terms = [[(c, index[id(node)], TERM_SLOT[w]) for c, node, w in l.terms] for l in loss_list]
     dsc_slot = None
     if per_channel_dice is not None and hasattr(per_channel_dice, "ptr"):
         for i, node in enumerate(nodes):

@@ -1,5 +1,5 @@
 """Device side of the loss: one fused statistics kernel + one backward kernel shared by
-CrossEntropyLoss and DiceLoss, and the scalar objects the training loop manipulates
+CrossEntropyLoss and DiceLoss, the BCELoss pair beside them, and the scalar objects the training loop manipulates
 (``sum(loss_list)``, ``coef * loss``, ``loss.backward()``, ``loss.numpy()[0]``;
 reference core/train.py:135-139,158)."""
 from __future__ import annotations
@@ -74,8 +74,66 @@ def node_for(logits: Tensor, labels) -> LossNode:
 _NODE_CACHE = {}
 
 
+class BCENode:
+    """BCELoss evaluation for one (logits, labels, settings) tuple: msk_bce_fwd / msk_bce_bwd.  out[0] is the loss (the
+    record has 2 + C floats like LossNode's, so the train loop's snapshot copies both kinds alike)."""
+
+    def __init__(self, logits: Tensor, labels: IntTensor, ignore_index: int, weight_mode: int, pos_weight_mode: int,
+                 pos_weight: float):
+        if tuple(labels.shape) != (logits.n, logits.d, logits.h, logits.w):
+            raise ValueError(f"label shape {labels.shape} does not match logits {logits.shape}")
+        self.logits, self.labels = logits, labels
+        self.dev = logits.dev
+        self.C = logits.c
+        self.ignore_index = int(ignore_index)
+        self.weight_mode, self.pos_weight_mode, self.pos_weight = int(weight_mode), int(pos_weight_mode), float(pos_weight)
+        self.out_ptr = None
+        self.stats_ptr = None
+
+    def evaluate(self):
+        if self.out_ptr is not None:
+            return
+        dev = self.dev
+        out = dev.arena.alloc((2 + self.C) * 4)
+        stats = dev.arena.alloc(8 * 8)
+        dev.call("msk_bce_fwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index, self.weight_mode,
+                 self.pos_weight_mode, C.c_float(self.pos_weight), C.c_void_p(out), C.c_void_p(stats))
+        self.out_ptr, self.stats_ptr = out, stats
+
+    def backward(self, coef: float, dz: Tensor | None = None) -> Tensor:
+        """coef * dBCE/dlogits written into a new tensor, or added into `dz` (the CE / Dice gradient of the same logits)."""
+        self.evaluate()
+        accumulate = dz is not None
+        if dz is None:
+            dz = self.logits.empty_like()
+        self.dev.call("msk_bce_bwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index,
+                      C.c_void_p(self.stats_ptr), C.c_float(coef), int(accumulate), dz.msk())
+        self.logits.grad = dz
+        self.logits.grad_written = True
+        return dz
+
+
+def bce_node_for(logits: Tensor, labels, ignore_index, weight_mode, pos_weight_mode, pos_weight) -> BCENode:
+    labels = to_tensor(labels, logits.dev)
+    key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), int(ignore_index), int(weight_mode),
+           int(pos_weight_mode), float(pos_weight))
+    node = _BCE_CACHE.get(key)
+    if node is None or node.logits is not logits:
+        if len(_BCE_CACHE) > 8:
+            _BCE_CACHE.clear()
+        node = BCENode(logits, labels, ignore_index, weight_mode, pos_weight_mode, pos_weight)
+        _BCE_CACHE[key] = node
+    return node
+
+
+_BCE_CACHE = {}
+
+# which float of a node's out record a term reads
+TERM_SLOT = {"ce": 0, "dice": 1, "bce": 0}
+
+
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (LossNode, 'ce'|'dice').  Values stay on
+    """A scalar loss = sum_i coef_i * term_i, term = (LossNode, 'ce'|'dice') or (BCENode, 'bce').  Values stay on
     the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 
@@ -106,7 +164,7 @@ class Scalar:
         for c, node, which in self.terms:
             node.evaluate()
             v = node.dev.d2h(node.out_ptr, (2,), np.float32)
-            tot += c * float(v[0 if which == "ce" else 1])
+            tot += c * float(v[TERM_SLOT[which]])
         return tot
 
     def numpy(self):
@@ -118,21 +176,31 @@ class Scalar:
     __float__ = value
 
     def backward(self):
-        groups = {}
+        # coefficients per node, the nodes grouped per logits tensor: the CE / Dice node writes dL/dlogits, every BCE node
+        # on the same logits adds into it (or writes it when it is the first)
+        per_logits = {}
         for c, node, which in self.terms:
-            g = groups.setdefault(id(node), [node, 0.0, 0.0])
-            if which == "ce":
-                g[1] += c
-            else:
+            group = per_logits.setdefault(id(node.logits), {})
+            g = group.setdefault(id(node), [node, 0.0, 0.0])
+            if which == "dice":
                 g[2] += c
+            else:
+                g[1] += c
         # dL/dlogits per evaluated output, then ONE backward per producing model: a
         # multi-output model (VNetDeepSup.num_outputs = 4) receives the list in forward order
         producers = {}
-        for node, cce, cdice in groups.values():
-            dz = node.backward(cce, cdice)
-            prod = node.logits.producer
+        for group in per_logits.values():
+            dz = None
+            for node, cce, cdice in group.values():
+                if isinstance(node, LossNode):
+                    dz = node.backward(cce, cdice)
+            for node, coef, _ in group.values():
+                if isinstance(node, BCENode):
+                    dz = node.backward(coef, dz)
+            logits = next(iter(group.values()))[0].logits
+            prod = logits.producer
             if prod is not None:
-                producers.setdefault(id(prod), (prod, {}))[1][getattr(node.logits, "out_index", 0)] = dz
+                producers.setdefault(id(prod), (prod, {}))[1][getattr(logits, "out_index", 0)] = dz
         for prod, grads in producers.values():
             n_out = getattr(prod, "num_outputs", 1)
             if n_out == 1:

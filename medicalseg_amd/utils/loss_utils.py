@@ -24,6 +24,9 @@ def _score(kind, loss_fn, logits_list, i, labels, edges):
         value, dice = loss_fn(logits, labels)
         return [value], dice
     if kind in _EDGE_LOSSES and getattr(loss_fn, 'edge_label', False):
+        if edges is None:   # the reference would fail inside the loss on edges=None
+            raise ValueError('{}(edge_label=True) needs edge maps, and none were given (the datasets of this package '
+                             'produce none): set edge_label=False'.format(kind))
         return [loss_fn(logits, edges)], None
     if kind == 'KLLoss':  # distillation: student vs detached teacher (outputs 0 and 1)
         return [loss_fn(logits_list[0], logits_list[1].detach())], None
