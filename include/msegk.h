@@ -507,6 +507,19 @@ int msk_max_norm(msk_ctx* ctx, const float* src, float* dst, size_t count);
 /* values.py:37-51 label_remap (sequential key->value passes) */
 int msk_label_remap(msk_ctx* ctx, int32_t* label, size_t count, const int32_t* keys,
                     const int32_t* vals, int npairs);
+/* transforms/functional.py:117-131 connected_component + RelabelComponent and
+ * transform.py:343-396 BinaryMaskToConnectComponent / TopkLargestConnectComponent: n independent
+ * contiguous d*h*w masks (dtype 0 = float32, 1 = int32; foreground = value != 0) -> int32 labels
+ * in dst (same shape, not aliasing src) of the 6-connected components, 1, 2, ... by decreasing
+ * size, ties by the first voxel in raster order; size < minimum_volume -> 0 and the later ranks
+ * close up; k > 0 also zeroes every rank above k (k <= 0 keeps all).  status[n] (device, required)
+ * receives per volume bit 0 = three or more distinct values (the reference's binary assert),
+ * bit 1 = an internal iteration bound was hit; counts[n] (device, may be NULL) the number of kept
+ * components.  Asynchronous: the caller reads status after synchronising.  n*d*h*w < 2^30;
+ * scratch about 2.1 int32 words per voxel.                                                  */
+int msk_connected_components3d(msk_ctx* ctx, const void* src, int32_t* dst, int n, int d, int h,
+                               int w, int dtype, int minimum_volume, int k, int32_t* status,
+                               int32_t* counts);
 
 /* Bias gradient of a convolution that feeds a BatchNorm, from the sums msk_affine_act_bwd_reduce
  * already produced (no extra pass over dy): with batch statistics sum_v dy[v][c] is identically 0

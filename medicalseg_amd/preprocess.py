@@ -9,6 +9,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._lib import MskError
 from .device import get_device
 
 
@@ -88,6 +89,55 @@ def max_normalize_device(vol: DeviceVolume) -> DeviceVolume:
     """transforms/transform.py:67-69 in place: im / im.max() when the maximum is positive."""
     vol.dev.call("msk_max_norm", C.c_void_p(vol.ptr), C.c_void_p(vol.ptr), C.c_size_t(vol.size))
     return vol
+
+
+def connected_components_device(x, minimum_volume=0, k=0):
+    """transforms/functional.py:117-131 connected_component (+ transform.py:343-396) on the device: the 6-connected
+    foreground components of every volume numbered 1, 2, ... by decreasing size (ties: first voxel in raster order),
+    components smaller than ``minimum_volume`` set to 0, with ``k > 0`` only the k largest kept.  Bitwise equal to
+    transforms.transform._connected_components per volume, as int32 instead of uint32.
+
+    x: a 3-D float32 / int32 ``DeviceVolume`` -> a new int32 ``DeviceVolume`` (pooled, like the other device ops); or an
+    ``IntTensor`` [N, 1, D, H, W] (core.infer.inference's prediction) -> a new ``IntTensor`` in the activation arena
+    (valid until the next model forward, like the prediction), each of the N volumes labelled on its own.  The input is
+    not modified.  Synchronises once, to read the per-volume status words: a volume with three or more distinct values
+    raises the host path's AssertionError."""
+    from .device import IntTensor
+    mv = int(min(max(np.ceil(minimum_volume), 0), 2 ** 31 - 1))   # integer sizes: size >= v  <=>  size >= ceil(v)
+    k = int(k)
+    if isinstance(x, DeviceVolume):
+        if len(x.shape) != 3:
+            raise ValueError("expected a 3-D volume, got shape {}".format(x.shape))
+        n, (d, h, w), dtype = 1, x.shape, _dt(x)
+        out = _pooled_volume(x.dev, x.shape, np.int32)
+        out_ptr = out.ptr
+    elif isinstance(x, IntTensor):
+        if len(x.shape) != 5 or x.shape[1] != 1:
+            raise ValueError("expected an [N, 1, D, H, W] label tensor, got shape {}".format(x.shape))
+        n, _, d, h, w = x.shape
+        dtype = 1
+        out = IntTensor(x.dev, x.dev.arena.alloc(int(np.prod(x.shape)) * 4), x.shape, x.dev.arena.gen)
+        out_ptr = out.ptr
+    else:
+        raise TypeError("connected_components_device takes a DeviceVolume or an IntTensor, got {}".format(type(x)))
+    dev = x.dev
+    st = _pool_alloc(dev, 4 * n)
+    try:
+        dev.call("msk_connected_components3d", C.c_void_p(x.ptr), C.c_void_p(out_ptr), n, d, h, w, dtype, mv, k,
+                 C.c_void_p(st), None)
+        status = dev.d2h(st, (n,), np.int32)
+    finally:
+        _pool_release(dev, st, 4 * n)
+    if status.any():
+        if isinstance(out, DeviceVolume):
+            out.free()
+        if (status & 2).any():
+            raise MskError("msk_connected_components3d: an iteration bound was hit (status {})".format(status.tolist()))
+        i = int(np.flatnonzero(status & 1)[0])
+        vol = x.numpy() if isinstance(x, DeviceVolume) else x.numpy()[i, 0]
+        vals = np.unique(vol)
+        raise AssertionError("Only binary mask is accepted, got mask with {}.".format(vals.tolist()))
+    return out
 
 
 def upload_pooled(image, dev=None) -> DeviceVolume:

@@ -281,24 +281,56 @@ def _connected_components(binary_mask, minimum_volume=0):
     return lut[lab]
 
 
+def _cc_on_device(x):
+    from ..device import IntTensor
+    return _on_device(x) or isinstance(x, IntTensor)
+
+
+def _cc_device(x, minimum_volume=0, k=0):
+    """a DeviceVolume is released like the other device ops' inputs (_swap); an IntTensor (inference()'s prediction,
+    arena memory) is left as it is"""
+    from ..preprocess import connected_components_device
+    out = connected_components_device(x, minimum_volume, k)
+    return _swap(x, out) if _on_device(x) else out
+
+
 @manager.TRANSFORMS.add_component
 class BinaryMaskToConnectComponent:
+    """numpy masks: the scipy path, uint32 labels.  A ``DeviceVolume`` or an ``IntTensor`` [N, 1, D, H, W] (the
+    prediction of core.infer.inference) takes the HIP path (preprocess.connected_components_device, every volume on its
+    own): int32 labels with the same values, on the device."""
+
     def __init__(self, minimum_volume=0):
         self.minimum_volume = minimum_volume
 
+    def _label(self, vol):
+        if _cc_on_device(vol):
+            return _cc_device(vol, self.minimum_volume)
+        return _connected_components(vol, self.minimum_volume)
+
     def __call__(self, pred, label=None):
-        pred = _connected_components(pred, self.minimum_volume)
+        pred = self._label(pred)
         if label is not None:
-            label = _connected_components(label, self.minimum_volume)
+            label = self._label(label)
         return pred, label
 
 
 @manager.TRANSFORMS.add_component
 class TopkLargestConnectComponent:
+    """numpy masks: the scipy path, uint32 labels.  A ``DeviceVolume`` or an ``IntTensor`` [N, 1, D, H, W] takes the HIP
+    path (preprocess.connected_components_device): int32 labels with the same values, on the device."""
+
     def __init__(self, k=1):
         self.k = k
 
     def __call__(self, pred, label=None):
+        if _cc_on_device(pred):
+            keep = int(np.floor(self.k))   # ranks r with r > k are dropped: k = 2.5 keeps 1 and 2
+            pred = _cc_device(pred, 0, max(keep, 0))
+            if keep < 1:   # the host path zeroes every label (still after the binary check)
+                n = pred.size if _on_device(pred) else int(np.prod(pred.shape))
+                pred.dev.memset(pred.ptr, 0, 4 * n)
+            return pred, label
         pred = _connected_components(pred)
         pred[pred > self.k] = 0
         return pred, label
