@@ -520,6 +520,16 @@ int msk_label_remap(msk_ctx* ctx, int32_t* label, size_t count, const int32_t* k
 int msk_connected_components3d(msk_ctx* ctx, const void* src, int32_t* dst, int n, int d, int h,
                                int w, int dtype, int minimum_volume, int k, int32_t* status,
                                int32_t* counts);
+/* utils/metric.py:21-61 calculate_area, as the confusion counts every hard-label metric (mean_iou, dice, accuracy,
+ * kappa: metric.py:110-210) is a sum of.  pred / label: n contiguous volumes of voxels_per_volume int32 values
+ * (4-byte alignment is enough).  counts (device): n rows of K*K + 1 unsigned 64-bit words, K = num_classes + 1:
+ * word r*K + c = voxels with label class r and predicted class c among the voxels whose label is not ignore_index,
+ * where class num_classes is "other" (a value < 0 or >= num_classes); the last word = voxels whose label is
+ * ignore_index.  So intersect_area[i] = word (i, i), pred_area[i] = column i, label_area[i] = row i (+ the last word
+ * when i == ignore_index).  accumulate != 0 adds to counts, 0 overwrites.  num_classes in [1, 64].  Exact (integer
+ * atomics only), asynchronous, nothing data-dependent can fail.                                                  */
+int msk_confusion3d(msk_ctx* ctx, const int32_t* pred, const int32_t* label, int n, long voxels_per_volume,
+                    int num_classes, int ignore_index, unsigned long long* counts, int accumulate);
 
 /* Bias gradient of a convolution that feeds a BatchNorm, from the sums msk_affine_act_bwd_reduce
  * already produced (no extra pass over dy): with batch statistics sum_v dy[v][c] is identically 0

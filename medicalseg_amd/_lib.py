@@ -149,6 +149,7 @@ SIGNATURES = {
     "msk_max_norm": (_i, [_vp, _vp, _vp, _sz]),
     "msk_label_remap": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     "msk_connected_components3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "msk_confusion3d": (_i, [_vp, _vp, _vp, _i, C.c_long, _i, _i, _vp, _i]),
     "msk_interp_trilinear_fwd": (_i, [_vp, _T, _T]),
     "msk_interp_scratch_bytes": (_i, [_vp, _T, _T, C.POINTER(_sz)]),
     "msk_interp_trilinear_bwd": (_i, [_vp, _T, _T, _i, _vp, _sz]),

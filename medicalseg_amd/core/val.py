@@ -45,7 +45,12 @@ def _image_info(dataset_json, idx):
 
 
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
-             save_dir=None):
+             save_dir=None, hard_metrics=False, pred_transform=None):
+    """hard_metrics: also score the hard-label prediction (the segmentation ``inference`` returns, passed through
+    ``pred_transform`` first when given: any callable IntTensor -> IntTensor, e.g. TopkLargestConnectComponent(k=1))
+    against the label on the device: confusion counts of every volume into one buffer (utils.metric.confusion_counts),
+    downloaded once after the loop.  Adds miou, dice (both pooled over the set), dice_per_case (mean over volumes of the
+    class-mean Dice), acc, kappa, class_iou, class_dice to the result.  ``mdice`` stays the soft V-Net Dice of the loss."""
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -64,6 +69,8 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     mdice = 0.0
     channel_dice_array = np.array([])
     loss_all = 0.0
+    counts = None                    # hard_metrics: [total_iters, K*K + 1] confusion counts on the device
+    num_classes, ignore_index = eval_dataset.num_classes, getattr(eval_dataset, "ignore_index", 255)
     logits_all, label_all = [], []   # auc_roc: softmax scores and labels of the whole set on the host (core/val.py:121-131)
     with nn.fused_inference():       # one scope for the whole set: BN is folded into the conv weights once
         for it, (im, label, idx) in enumerate(loader):
@@ -73,6 +80,13 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                                            transforms=eval_dataset.transforms.transforms)
             loss, per_channel_dice = loss_computation(logits, label_t, new_loss)
             loss = sum(loss)
+            if hard_metrics:
+                if counts is None:
+                    counts = metric.ConfusionCounts(pred.dev, total_iters, num_classes, ignore_index, zero=True)
+                hard = pred_transform(pred) if pred_transform is not None else pred
+                if isinstance(hard, tuple):     # the transform classes return (pred, label)
+                    hard = hard[0]
+                metric.confusion_counts(hard, label_t, num_classes, ignore_index, out=counts.rows(it, len(label)))
             if auc_roc:
                 lg = logits[0] if isinstance(logits, (list, tuple)) else logits
                 probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
@@ -103,8 +117,26 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         auc = metric.auc_roc(np.concatenate(logits_all), np.concatenate(label_all), num_classes=eval_dataset.num_classes)
         auc_infor = ' Auc_roc: {:.4f}'.format(auc)
         result_dict['auc_roc'] = auc
+    hard_infor = None
+    if hard_metrics and counts is not None:
+        c = counts.numpy()
+        counts.free()
+        areas = metric.areas_from_counts(c, num_classes, ignore_index)
+        class_iou, miou = metric.mean_iou(*areas)
+        class_dice, hdice = metric.dice(*areas)
+        _, acc = metric.accuracy(areas[0], areas[1])
+        kappa = metric.kappa(*areas)
+        dice_per_case = float(np.mean(metric.per_case(c, num_classes, ignore_index)["mdice"]))
+        result_dict.update(miou=float(miou), dice=float(hdice), dice_per_case=dice_per_case, acc=float(acc),
+                           kappa=float(kappa), class_iou=class_iou, class_dice=class_dice)
+        hard_infor = ("[EVAL] Hard labels: mIoU: {:.4f}, Dice: {:.4f}, Dice per case: {:.4f}, Acc: {:.4f}, Kappa: {:.4f}".format(
+            miou, hdice, dice_per_case, acc, kappa),
+            "[EVAL] Class IoU: \n" + str(np.round(class_iou, 4)) + "\n[EVAL] Class hard dice: \n" + str(np.round(class_dice, 4)))
     if print_detail and local_rank == 0:
         logger.info("[EVAL] #Images: {}, Dice: {:.4f}, Loss: {:6f}".format(len(eval_dataset), mdice,
                                                                            float(np.ravel(loss_all)[0])) + auc_infor)
         logger.info("[EVAL] Class dice: \n" + str(np.round(channel_dice_array, 4)))
+        if hard_infor is not None:
+            logger.info(hard_infor[0])
+            logger.info(hard_infor[1])
     return result_dict

@@ -1,4 +1,5 @@
-"""Host-side metrics of the evaluation loop.
+"""Metrics of the evaluation loop: auc_roc on the host; the hard-label family (calculate_area, mean_iou, dice, accuracy,
+kappa) from confusion counts taken on the device (second half of this file).
 
 auc_roc: area under the ROC curve of the softmax scores collected by ``core.val.evaluate(auc_roc=True)`` -- the quantity the
 reference takes from ``sklearn.metrics.roc_auc_score`` (medicalseg/utils/metric.py:64-107): binary = AUC of the class-1
@@ -56,3 +57,202 @@ def auc_roc(logits, label, num_classes, ignore_index=None):
     if len(present) != C:
         raise ValueError("Number of classes in y_true not equal to the number of columns in 'y_score'")
     return float(np.mean([binary_auc(scores[:, c], lab == c) for c in range(C)]))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Hard-label metrics (reference medicalseg/utils/metric.py:21-61, 110-210): calculate_area, mean_iou, dice, accuracy,
+# kappa.  Everything is derived from the CONFUSION COUNTS of a prediction against its label, one row per volume:
+# K*K + 1 words with K = num_classes + 1, word r*K + c = voxels with label class r and predicted class c among the
+# voxels whose label is not ignore_index (class num_classes = "other": negative or >= num_classes), last word =
+# voxels whose label is ignore_index.  Device inputs are counted by msk_confusion3d (csrc/msk_metrics.hip) and only
+# the counts are downloaded; numpy inputs take the same definition through np.bincount.
+
+
+class ConfusionCounts:
+    """[N, K*K + 1] uint64 confusion counts in a persistent device buffer (not the activation arena: it survives the
+    next model forward).  Passing it back as ``confusion_counts(..., out=self)`` adds to it; ``numpy()`` downloads
+    (one synchronisation)."""
+
+    def __init__(self, dev, n, num_classes, ignore_index=255, zero=False, _view_of=None):
+        self.dev, self.n, self.num_classes, self.ignore_index = dev, int(n), int(num_classes), int(ignore_index)
+        self.shape = (self.n, (self.num_classes + 1) ** 2 + 1)
+        self._owner = _view_of      # a view keeps its parent alive and does not free
+        if _view_of is None:
+            self.ptr = dev.malloc(self.shape[0] * self.shape[1] * 8)
+            if zero:
+                dev.memset(self.ptr, 0, self.shape[0] * self.shape[1] * 8)
+
+    def rows(self, start, count=1):
+        """rows [start, start + count) as a ConfusionCounts of their own (same memory): the ``out=`` of one batch of a
+        validation set whose buffer (created with ``zero=True``) holds one row per volume"""
+        start, count = int(start), int(count)
+        if not (0 <= start and count >= 1 and start + count <= self.n):
+            raise IndexError("rows [{}, {}) of {}".format(start, start + count, self.n))
+        v = ConfusionCounts(self.dev, count, self.num_classes, self.ignore_index, _view_of=self)
+        v.ptr = self.ptr + start * self.shape[1] * 8
+        return v
+
+    def numpy(self):
+        return self.dev.d2h(self.ptr, self.shape, np.uint64)
+
+    def free(self):
+        if self._owner is None and self.ptr:
+            self.dev.free(self.ptr)
+        self.ptr = None
+
+
+def _is_device(x):
+    from ..device import IntTensor
+    from ..preprocess import DeviceVolume
+    return isinstance(x, (IntTensor, DeviceVolume))
+
+
+def _volume_shape(x):
+    """(N, spatial shape) of a prediction / label: [N, 1, D, H, W], [N, D, H, W] or one 3-D volume"""
+    shape = tuple(int(s) for s in x.shape)
+    if len(shape) == 5 and shape[1] == 1:
+        shape = shape[:1] + shape[2:]
+    if len(shape) == 3:
+        shape = (1,) + shape
+    if len(shape) != 4:
+        raise ValueError("expected [N, 1, D, H, W], [N, D, H, W] or [D, H, W], got shape {}".format(tuple(x.shape)))
+    return shape[0], shape[1:]
+
+
+def confusion_counts(pred, label, num_classes, ignore_index=255, out=None):
+    """Confusion counts of ``pred`` against ``label``, one row per volume (layout above).
+
+    Device inputs (``IntTensor`` [N, 1, D, H, W] / [N, D, H, W], or a 3-D int32 ``DeviceVolume``; both on one
+    device): one msk_confusion3d launch, no synchronisation; returns a ``ConfusionCounts``.  ``out`` (an earlier
+    result with the same N, num_classes and ignore_index) is added to and returned.  numpy inputs: the same counts as
+    an [N, K*K + 1] uint64 array on the host (``out``: an array that is added to in place)."""
+    num_classes, ignore_index = int(num_classes), int(ignore_index)
+    if not 1 <= num_classes <= 64:
+        raise ValueError("num_classes must be in [1, 64], got {}".format(num_classes))
+    dev_in = (_is_device(pred), _is_device(label))
+    if dev_in[0] != dev_in[1]:
+        raise TypeError("pred and label must both be device arrays or both be host arrays")
+    if not dev_in[0]:
+        pred, label = np.asarray(pred), np.asarray(label)
+    (n, ps), (nl, ls) = _volume_shape(pred), _volume_shape(label)
+    if (n, ps) != (nl, ls):
+        raise ValueError('Shape of `pred` and `label should be equal, but there are {} and {}.'.format(
+            list((n,) + ps), list((nl,) + ls)))
+    K = num_classes + 1
+    B = K * K + 1
+    if dev_in[0]:
+        import ctypes as C
+        if pred.dev is not label.dev:
+            raise ValueError("pred and label are on different devices")
+        for x in (pred, label):
+            if getattr(x, "dtype", np.dtype(np.int32)) != np.int32:
+                raise TypeError("device volumes must be int32, got {}".format(x.dtype))
+        if out is None:
+            res, acc = ConfusionCounts(pred.dev, n, num_classes, ignore_index), 0
+        else:
+            if not isinstance(out, ConfusionCounts) or out.dev is not pred.dev or \
+                    (out.n, out.num_classes, out.ignore_index) != (n, num_classes, ignore_index):
+                raise ValueError("`out` must be a ConfusionCounts of the same device, N, num_classes and ignore_index")
+            res, acc = out, 1
+        pred.dev.call("msk_confusion3d", C.c_void_p(pred.ptr), C.c_void_p(label.ptr), n, C.c_long(int(np.prod(ps))),
+                      num_classes, ignore_index, C.c_void_p(res.ptr), acc)
+        return res
+    p = pred.reshape(n, -1).astype(np.int64)
+    l = label.reshape(n, -1).astype(np.int64)
+    r = np.where((l >= 0) & (l < num_classes), l, num_classes)
+    c = np.where((p >= 0) & (p < num_classes), p, num_classes)
+    key = np.where(l == ignore_index, K * K, r * K + c)
+    counts = np.stack([np.bincount(k, minlength=B) for k in key]).astype(np.uint64)
+    if out is not None:
+        if not isinstance(out, np.ndarray) or out.shape != counts.shape:
+            raise ValueError("`out` must be an array of shape {}".format(counts.shape))
+        out += counts.astype(out.dtype)
+        return out
+    return counts
+
+
+def _host(x):
+    return np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+
+
+def areas_from_counts(counts, num_classes, ignore_index=255, per_volume=False):
+    """(intersect_area, pred_area, label_area) of the reference's calculate_area from confusion counts: int64 arrays
+    of length num_classes summed over the rows, or [N, num_classes] with ``per_volume``.  label_area counts
+    ``label == i`` without the ignore mask, as the reference does: the ignored voxels return to class ignore_index."""
+    num_classes, ignore_index = int(num_classes), int(ignore_index)
+    K = num_classes + 1
+    c = _host(counts).astype(np.int64).reshape(-1, K * K + 1)
+    m = c[:, :K * K].reshape(-1, K, K)
+    idx = np.arange(num_classes)
+    intersect = m[:, idx, idx]
+    pred_area = m.sum(axis=1)[:, :num_classes]
+    label_area = m.sum(axis=2)[:, :num_classes].copy()
+    if 0 <= ignore_index < num_classes:
+        label_area[:, ignore_index] += c[:, -1]
+    if per_volume:
+        return intersect, pred_area, label_area
+    return intersect.sum(axis=0), pred_area.sum(axis=0), label_area.sum(axis=0)
+
+
+def calculate_area(pred, label, num_classes, ignore_index=255):
+    """metric.py:21-61 -> (intersect_area, pred_area, label_area), int64 [num_classes], summed over the batch.
+    Device inputs are counted on the device (one download of the counts)."""
+    counts = confusion_counts(pred, label, num_classes, ignore_index)
+    try:
+        return areas_from_counts(counts, num_classes, ignore_index)
+    finally:
+        if isinstance(counts, ConfusionCounts):
+            counts.free()
+
+
+def _ratio(num, den):
+    """num / den per class in float64, 0 where den == 0"""
+    num, den = _host(num).astype(np.float64), _host(den).astype(np.float64)
+    out = np.zeros(num.shape, dtype=np.float64)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+def mean_iou(intersect_area, pred_area, label_area):
+    """metric.py:110-135 -> (class_iou, miou); a class with an empty union scores 0 and still enters the mean"""
+    i, p, l = _host(intersect_area), _host(pred_area), _host(label_area)
+    class_iou = _ratio(i, p + l - i)
+    return class_iou, np.mean(class_iou)
+
+
+def dice(intersect_area, pred_area, label_area):
+    """metric.py:138-163 -> (class_dice, mdice); 2 |A n B| / (|A| + |B|), 0 for a class absent from both"""
+    i, p, l = _host(intersect_area), _host(pred_area), _host(label_area)
+    class_dice = _ratio(2 * i, p + l)
+    return class_dice, np.mean(class_dice)
+
+
+def accuracy(intersect_area, pred_area):
+    """metric.py:166-188 -> (class_acc, macc); macc is the overall ratio sum(intersect) / sum(pred), not the class mean"""
+    i, p = _host(intersect_area), _host(pred_area)
+    return _ratio(i, p), np.sum(i) / np.sum(p)
+
+
+def kappa(intersect_area, pred_area, label_area):
+    """metric.py:191-210 Cohen's kappa (po - pe) / (1 - pe); not guarded against pe == 1, as in the reference"""
+    i, p, l = _host(intersect_area), _host(pred_area), _host(label_area)
+    total = np.sum(l)
+    po = np.sum(i) / total
+    pe = np.sum(p * l) / (total * total)
+    return (po - pe) / (1 - pe)
+
+
+def per_case(counts, num_classes, ignore_index=255):
+    """The same metrics per volume (medical results are means over cases; the functions above pool the voxels):
+    {'class_iou', 'class_dice', 'class_acc': [N, num_classes]; 'miou', 'mdice', 'acc', 'kappa': [N]} from the
+    [N, K*K + 1] counts."""
+    rows = areas_from_counts(counts, num_classes, ignore_index, per_volume=True)
+    res = {k: [] for k in ("class_iou", "miou", "class_dice", "mdice", "class_acc", "acc", "kappa")}
+    for i, p, l in zip(*rows):
+        ci, mi = mean_iou(i, p, l)
+        cd, md = dice(i, p, l)
+        ca, ma = accuracy(i, p)
+        for k, v in (("class_iou", ci), ("miou", mi), ("class_dice", cd), ("mdice", md), ("class_acc", ca), ("acc", ma),
+                     ("kappa", kappa(i, p, l))):
+            res[k].append(v)
+    return {k: np.asarray(v, dtype=np.float64) for k, v in res.items()}
