@@ -530,6 +530,27 @@ int msk_connected_components3d(msk_ctx* ctx, const void* src, int32_t* dst, int 
  * atomics only), asynchronous, nothing data-dependent can fail.                                                  */
 int msk_confusion3d(msk_ctx* ctx, const int32_t* pred, const int32_t* label, int n, long voxels_per_volume,
                     int num_classes, int ignore_index, unsigned long long* counts, int accumulate);
+/* core/val.py:121-131,174 + utils/metric.py:64-107 auc_roc (sklearn.metrics.roc_auc_score of the softmax scores of the
+ * whole validation set, one-vs-rest): stage 1 of 2.  probs: the output of msk_softmax_c, V = n*d*h*w voxels of C = probs.c
+ * scores; label: V int32 class indices.  keys (device): C streams of `capacity` 32-bit words, class-major; the call writes
+ * keys[c * capacity + offset + v] = bits(probs[v][c]) | (label[v] == c) << 31 for every class, -0.0 folded onto +0.0
+ * (offset + V <= capacity < 2^31).  status (device, two 64-bit words, zeroed by the caller once): [0] += voxels whose label
+ * is outside [0, C), [1] += scores that are negative or not finite (their keys are meaningless).  Asynchronous, no host
+ * synchronisation; the inputs are not modified.                                                                        */
+int msk_auc_pack(msk_ctx* ctx, msk_tensor probs, const int32_t* label, uint32_t* keys, long capacity, long offset,
+                 unsigned long long* status);
+/* bytes of scratch msk_auc_counts needs for `count` keys per class (host arithmetic only: no context, no GPU): a second key
+ * buffer of 4 * classes * count bytes plus the histograms of the sort, about 1/16 of that.  count in [1, 2^31), classes
+ * in [1, 64].                                                                                                          */
+int msk_auc_workspace(long count, int classes, size_t* bytes);
+/* core/val.py:121-131,174 + utils/metric.py:64-107 auc_roc, stage 2 of 2: sorts the first `count` keys of every class in
+ * place (radix sort on bits 0-30, bit 31 carried; the sorted buffer is still a valid bag of keys that msk_auc_pack may
+ * append to) and writes out[c] = {U2, n_pos, n_neg} (device, classes x 3 unsigned 64-bit words) with
+ *   U2 = sum over the positives i of 2 * #{negatives with a smaller score} + #{negatives with an equal score},
+ * so that AUC(c) = U2 / (2 * n_pos * n_neg).  Exact integers, independent of the schedule; asynchronous.  workspace:
+ * device memory of at least msk_auc_workspace(count, classes) bytes, 16-byte aligned.                                  */
+int msk_auc_counts(msk_ctx* ctx, uint32_t* keys, long capacity, long count, int classes, void* workspace,
+                   size_t workspace_bytes, unsigned long long* out);
 
 /* Bias gradient of a convolution that feeds a BatchNorm, from the sums msk_affine_act_bwd_reduce
  * already produced (no extra pass over dy): with batch statistics sum_v dy[v][c] is identically 0

@@ -150,6 +150,9 @@ SIGNATURES = {
     "msk_label_remap": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     "msk_connected_components3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "msk_confusion3d": (_i, [_vp, _vp, _vp, _i, C.c_long, _i, _i, _vp, _i]),
+    "msk_auc_pack": (_i, [_vp, _T, _vp, _vp, C.c_long, C.c_long, _vp]),
+    "msk_auc_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),
+    "msk_auc_counts": (_i, [_vp, _vp, C.c_long, C.c_long, _i, _vp, _sz, _vp]),
     "msk_interp_trilinear_fwd": (_i, [_vp, _T, _T]),
     "msk_interp_scratch_bytes": (_i, [_vp, _T, _T, C.POINTER(_sz)]),
     "msk_interp_trilinear_bwd": (_i, [_vp, _T, _T, _i, _vp, _sz]),

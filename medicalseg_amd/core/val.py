@@ -45,8 +45,12 @@ def _image_info(dataset_json, idx):
 
 
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
-             save_dir=None, hard_metrics=False, pred_transform=None):
-    """hard_metrics: also score the hard-label prediction (the segmentation ``inference`` returns, passed through
+             save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False):
+    """auc_device (with auc_roc): the softmax scores of every volume stay on the device as sortable keys
+    (utils.metric.AucScores) and the AUC comes from exact pair counts taken there, downloaded once after the loop --
+    the same float as the host path, without the download of the probabilities and the host sorts.
+
+    hard_metrics: also score the hard-label prediction (the segmentation ``inference`` returns, passed through
     ``pred_transform`` first when given: any callable IntTensor -> IntTensor, e.g. TopkLargestConnectComponent(k=1))
     against the label on the device: confusion counts of every volume into one buffer (utils.metric.confusion_counts),
     downloaded once after the loop.  Adds miou, dice (both pooled over the set), dice_per_case (mean over volumes of the
@@ -72,6 +76,7 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     counts = None                    # hard_metrics: [total_iters, K*K + 1] confusion counts on the device
     num_classes, ignore_index = eval_dataset.num_classes, getattr(eval_dataset, "ignore_index", 255)
     logits_all, label_all = [], []   # auc_roc: softmax scores and labels of the whole set on the host (core/val.py:121-131)
+    auc_scores = None                # auc_roc with auc_device: the same scores as keys on the device
     with nn.fused_inference():       # one scope for the whole set: BN is folded into the conv weights once
         for it, (im, label, idx) in enumerate(loader):
             reader_cost_averager.record(time.time() - batch_start)
@@ -91,8 +96,13 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                 lg = logits[0] if isinstance(logits, (list, tuple)) else logits
                 probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
                 lg.dev.call("msk_softmax_c", lg.msk(), probs.msk())       # F.softmax(logits, axis=1) on the device
-                logits_all.append(probs.numpy())
-                label_all.append(np.asarray(label))
+                if auc_device:
+                    if auc_scores is None:      # room for the whole set at the size of the first volume; grows otherwise
+                        auc_scores = metric.AucScores(lg.dev, num_classes, total_iters * probs.voxels)
+                    auc_scores.add(probs, label_t)
+                else:
+                    logits_all.append(probs.numpy())
+                    label_all.append(np.asarray(label))
             loss_all += loss.numpy()
             pcd = np.asarray(per_channel_dice)
             mdice += np.mean(pcd)
@@ -114,7 +124,15 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     result_dict = {"mdice": float(mdice)}
     auc_infor = ""
     if auc_roc:
-        auc = metric.auc_roc(np.concatenate(logits_all), np.concatenate(label_all), num_classes=eval_dataset.num_classes)
+        if auc_device:
+            if auc_scores is None:
+                raise ValueError("evaluate(auc_roc=True, auc_device=True): the dataset is empty")
+            try:
+                auc = metric.auc_from_counts(auc_scores.counts(), eval_dataset.num_classes)
+            finally:
+                auc_scores.free()
+        else:
+            auc = metric.auc_roc(np.concatenate(logits_all), np.concatenate(label_all), num_classes=eval_dataset.num_classes)
         auc_infor = ' Auc_roc: {:.4f}'.format(auc)
         result_dict['auc_roc'] = auc
     hard_infor = None

@@ -1,4 +1,5 @@
-"""Metrics of the evaluation loop: auc_roc on the host; the hard-label family (calculate_area, mean_iou, dice, accuracy,
+"""Metrics of the evaluation loop: auc_roc on the host, or for device inputs from exact pair counts taken on the device
+(auc_counts / AucScores / auc_from_counts below); the hard-label family (calculate_area, mean_iou, dice, accuracy,
 kappa) from confusion counts taken on the device (second half of this file).
 
 auc_roc: area under the ROC curve of the softmax scores collected by ``core.val.evaluate(auc_roc=True)`` -- the quantity the
@@ -38,7 +39,23 @@ def binary_auc(score, positive):
 
 
 def auc_roc(logits, label, num_classes, ignore_index=None):
-    """logits: softmax scores (N, C, *spatial); label: (N, 1, *spatial) or (N, *spatial) class indices."""
+    """logits: softmax scores (N, C, *spatial); label: (N, 1, *spatial) or (N, *spatial) class indices.
+    A device ``Tensor`` of scores with an ``IntTensor`` label (both on one device) is counted on the device
+    (AucScores): the same float, and only the 3 * C + 2 count words are downloaded."""
+    from ..device import IntTensor, Tensor
+    if isinstance(logits, Tensor) or isinstance(label, IntTensor):
+        if not (isinstance(logits, Tensor) and isinstance(label, IntTensor)):
+            raise TypeError("logits and label must both be device arrays or both be host arrays")
+        if ignore_index:
+            raise RuntimeError('labels with ignore_index is not supported yet.')
+        if logits.c != num_classes:
+            raise ValueError("logits have {} channels, num_classes is {}".format(logits.c, num_classes))
+        acc = AucScores(logits.dev, num_classes, logits.voxels)
+        try:
+            acc.add(logits, label)
+            return auc_from_counts(acc.counts(), num_classes)
+        finally:
+            acc.free()
     logits = np.asarray(logits)
     label = np.asarray(label)
     if ignore_index or len(np.unique(label)) > num_classes:
@@ -57,6 +74,174 @@ def auc_roc(logits, label, num_classes, ignore_index=None):
     if len(present) != C:
         raise ValueError("Number of classes in y_true not equal to the number of columns in 'y_score'")
     return float(np.mean([binary_auc(scores[:, c], lab == c) for c in range(C)]))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# auc_roc from exact pair counts.  With float32 scores the one-vs-rest AUC of class c is U2 / (2 * n_pos * n_neg) where
+#   U2 = sum over the positives i of ( 2 * #{negatives j : s_j < s_i} + #{negatives j : s_j == s_i} )
+# is an integer: twice the Mann-Whitney statistic binary_auc takes from average ranks.  On the sorted scores, with N(p) the
+# negatives in front of position p, a positive inside the run of equal scores [a, b) contributes N(a) + N(b).
+# auc_counts states this in numpy; csrc/msk_auc.hip (msk_auc_pack / msk_auc_counts, through AucScores) is held to it word
+# for word.  auc_from_counts turns the [C, 3] words {U2, n_pos, n_neg} into the float auc_roc returns.
+
+
+def _check_scores_and_labels(bad_label, bad_score):
+    if bad_label:
+        raise RuntimeError('labels with ignore_index is not supported yet.')
+    if bad_score:
+        raise ValueError("{} scores are negative or not finite: not softmax outputs".format(int(bad_score)))
+
+
+def auc_counts(scores, label, num_classes):
+    """[C, 3] uint64 {U2, n_pos, n_neg} per class from float32 scores (N, C, *spatial) and labels (N, 1, *spatial) or
+    (N, *spatial), on the host: sort, runs of equal scores, prefix counts of the negatives.  Scores must be finite and
+    >= 0 (-0.0 counts as 0.0), labels inside [0, C)."""
+    scores = np.asarray(scores, dtype=np.float32)
+    label = np.asarray(label)
+    if scores.ndim < 2:
+        raise ValueError('The shape of logits is not (N, C, *spatial), it is {}'.format(scores.shape))
+    C = scores.shape[1]
+    if C != num_classes:
+        raise ValueError("scores have {} channels, num_classes is {}".format(C, num_classes))
+    sc = np.ascontiguousarray(np.moveaxis(scores, 1, -1).reshape(-1, C))
+    lab = label.reshape(-1)
+    if sc.shape[0] != lab.shape[0]:
+        raise ValueError('length of `logit` and `label` should be equal, but they are {} and {}.'.format(sc.shape[0],
+                                                                                                    lab.shape[0]))
+    bits = sc.view(np.uint32)
+    bits = np.where(bits == 0x80000000, np.uint32(0), bits)
+    bad_score = np.count_nonzero((bits & 0x80000000) != 0) + np.count_nonzero((bits & 0x7f800000) == 0x7f800000)
+    _check_scores_and_labels(np.count_nonzero((lab < 0) | (lab >= C)), bad_score)
+    out = np.zeros((C, 3), dtype=np.uint64)
+    n = lab.shape[0]
+    for c in range(C):
+        # bits of a non-negative float are in float order; the flag rides in bit 0 (its order inside a run does not matter)
+        k = np.sort((bits[:, c] << np.uint32(1)) | (lab == c).astype(np.uint32))
+        positive = (k & 1).astype(bool)
+        xs = k >> 1
+        start = np.flatnonzero(np.concatenate(([True], xs[1:] != xs[:-1]))) if n else np.zeros(0, np.int64)
+        end = np.concatenate((start[1:], [n])).astype(np.int64)
+        nneg = np.concatenate(([0], np.cumsum(~positive, dtype=np.int64)))       # N(p), p = 0 .. n
+        npos_run = np.add.reduceat(positive.astype(np.int64), start) if n else np.zeros(0, np.int64)
+        u2 = int(np.sum(npos_run * (nneg[start] + nneg[end])))                   # <= 2 n_pos n_neg < 2^62: exact in int64
+        n_neg = int(nneg[-1])
+        out[c] = (u2, n - n_neg, n_neg)
+    return out
+
+
+def auc_from_counts(counts, num_classes):
+    """The float ``auc_roc`` returns from [C, 3] {U2, n_pos, n_neg}: two classes -> AUC of class 1; more -> macro
+    one-vs-rest over all classes, every one of which needs a positive (metric.py:64-107 / sklearn's conventions)."""
+    c = np.asarray(counts).reshape(-1, 3)
+    if c.shape[0] != num_classes:
+        raise ValueError("counts have {} rows, num_classes is {}".format(c.shape[0], num_classes))
+
+    def one(row):
+        u2, n_pos, n_neg = (int(v) for v in row)
+        if n_pos == 0 or n_neg == 0:
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        return float(u2) / (2.0 * n_pos * n_neg)
+
+    if num_classes == 2:
+        return one(c[1])
+    if any(int(row[1]) == 0 for row in c):
+        raise ValueError("Number of classes in y_true not equal to the number of columns in 'y_score'")
+    return float(np.mean([one(row) for row in c]))
+
+
+class AucScores:
+    """The softmax scores of a whole validation set as sortable keys in persistent device buffers (not the activation
+    arena), and their exact AUC counts.
+
+    ``add(probs, label)`` appends one batch (msk_auc_pack at the current fill: no synchronisation); the buffers grow by
+    a device-to-device copy when ``capacity`` (keys per class) is exceeded.  ``counts()`` sorts and counts on the device
+    (msk_auc_counts) and downloads 3 * C + 2 words, the one synchronisation: the [C, 3] uint64 {U2, n_pos, n_neg} of
+    ``auc_counts``.  It raises RuntimeError('labels with ignore_index is not supported yet.') when a label was outside
+    [0, C) and ValueError for a negative or non-finite score.  ``add`` after ``counts()`` keeps working.
+
+    Device memory: 4 * C * capacity bytes of keys for the lifetime of the object, and inside ``counts()`` a second
+    buffer of 4 * C * fill bytes plus the histograms of the sort (about 1/16 of it): 2 * 4 * C * capacity bytes plus
+    the histograms at the peak."""
+
+    def __init__(self, dev, num_classes, capacity):
+        self.dev, self.num_classes = dev, int(num_classes)
+        if not 1 <= self.num_classes <= 64:
+            raise ValueError("num_classes must be in [1, 64], got {}".format(num_classes))
+        self.capacity = self._round(max(int(capacity), 1))
+        self.fill = 0
+        self.keys = self._malloc(4 * self.num_classes * self.capacity, self.capacity)
+        # {U2, n_pos, n_neg} per class, then the two status words of msk_auc_pack: one download
+        self.words = 3 * self.num_classes + 2
+        self.res = dev.malloc(8 * self.words)
+        dev.memset(self.res, 0, 8 * self.words)
+
+    @staticmethod
+    def _round(n):
+        return (n + 3) & ~3       # every class stream starts on 16 bytes
+
+    def _malloc(self, nbytes, capacity):
+        from .._lib import MskError
+        try:
+            return self.dev.malloc(nbytes)
+        except MskError as e:
+            raise MskError("AucScores: {} bytes of device memory for {} classes x {} keys failed (it needs 2 x 4 x "
+                           "classes x capacity = {} bytes plus the histograms): {}".format(
+                               nbytes, self.num_classes, capacity, 8 * self.num_classes * capacity, e)) from None
+
+    def _grow(self, need):
+        cap = self._round(max(need, 2 * self.capacity))
+        if cap >= 2 ** 31:
+            cap = self._round(need)
+        if cap >= 2 ** 31:
+            raise ValueError("AucScores holds fewer than 2^31 scores per class, {} requested".format(need))
+        new = self._malloc(4 * self.num_classes * cap, cap)
+        for c in range(self.num_classes if self.fill else 0):
+            self.dev.d2d(new + 4 * c * cap, self.keys + 4 * c * self.capacity, 4 * self.fill)
+        self.dev.free(self.keys)
+        self.keys, self.capacity = new, cap
+
+    def add(self, probs, label):
+        import ctypes as C
+        from ..device import IntTensor, Tensor
+        if not isinstance(probs, Tensor) or not isinstance(label, IntTensor):
+            raise TypeError("AucScores.add takes a device Tensor of scores and an IntTensor label")
+        if probs.dev is not self.dev or label.dev is not self.dev:
+            raise ValueError("scores, label and AucScores are on different devices")
+        if probs.c != self.num_classes:
+            raise ValueError("scores have {} channels, num_classes is {}".format(probs.c, self.num_classes))
+        v = probs.voxels
+        if int(np.prod(label.shape)) != v:
+            raise ValueError('length of `logit` and `label` should be equal, but they are {} and {}.'.format(
+                v, int(np.prod(label.shape))))
+        if self.fill + v > self.capacity:
+            self._grow(self.fill + v)
+        self.dev.call("msk_auc_pack", probs.msk(), C.c_void_p(label.ptr), C.c_void_p(self.keys), C.c_long(self.capacity),
+                      C.c_long(self.fill), C.c_void_p(self.res + 8 * 3 * self.num_classes))
+        self.fill += v
+
+    def counts(self):
+        import ctypes as C
+        if self.fill == 0:
+            raise ValueError("AucScores.counts: no scores were added")
+        nbytes = C.c_size_t(0)
+        if self.dev.lib.msk_auc_workspace(C.c_long(self.fill), self.num_classes, C.byref(nbytes)) != 0:
+            from .._lib import MskError, last_error
+            raise MskError("msk_auc_workspace failed: " + last_error(None))
+        ws = self._malloc(nbytes.value, self.capacity)
+        try:
+            self.dev.call("msk_auc_counts", C.c_void_p(self.keys), C.c_long(self.capacity), C.c_long(self.fill),
+                          self.num_classes, C.c_void_p(ws), nbytes, C.c_void_p(self.res))
+            words = self.dev.d2h(self.res, (self.words,), np.uint64)
+        finally:
+            self.dev.free(ws)
+        _check_scores_and_labels(int(words[-2]), int(words[-1]))
+        return words[:3 * self.num_classes].reshape(self.num_classes, 3).copy()
+
+    def free(self):
+        if self.keys:
+            self.dev.free(self.keys)
+            self.dev.free(self.res)
+        self.keys = self.res = None
 
 
 # ------------------------------------------------------------------------------------------------------------------

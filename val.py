@@ -15,6 +15,8 @@ def parse_args():
     p.add_argument('--num_workers', dest='num_workers', help='Num workers for data loader', type=int, default=0)
     p.add_argument('--print_detail', dest='print_detail', type=bool, default=True)
     p.add_argument('--auc_roc', dest='auc_roc', help='Whether to use auc_roc metric', type=bool, default=False)
+    p.add_argument('--auc_device', dest='auc_device', type=bool, default=False,
+                   help='With --auc_roc: keep the scores on the GPU and compute the AUC there (same value)')
     p.add_argument('--hard_metrics', dest='hard_metrics', type=bool, default=False,
                    help='Whether to report the hard-label metrics (mIoU, Dice, accuracy, kappa) of the prediction')
     return p.parse_args()
@@ -35,7 +37,7 @@ def main(args):
         load_entire_model(model, args.model_path)
         logger.info('Loaded trained params of model successfully')
     print(evaluate(model, val_dataset, cfg.loss, num_workers=args.num_workers, print_detail=args.print_detail,
-                   auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics))
+                   auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device))
 
 
 if __name__ == '__main__':
