@@ -551,6 +551,28 @@ int msk_auc_workspace(long count, int classes, size_t* bytes);
  * device memory of at least msk_auc_workspace(count, classes) bytes, 16-byte aligned.                                  */
 int msk_auc_counts(msk_ctx* ctx, uint32_t* keys, long capacity, long count, int classes, void* workspace,
                    size_t workspace_bytes, unsigned long long* out);
+/* Boundary metrics (Hausdorff, HD95, average symmetric surface distance; the reference has none: medpy's conventions,
+ * utils/metric.py surface_distances), stage 1: exact squared Euclidean distance transform of the int32 volume vol[d][h][w]
+ * (axes z, y, x).  Features = the voxels with vol == cls, or with surface_only != 0 their surface: the voxels of that set
+ * with at least one of the six face neighbours outside it (beyond the volume's edge counts as outside).  spacing (HOST
+ * pointer, nullable = 1, 1, 1): sz, sy, sx; w_ = spacing_^2 rounded once.  dist2 (device, d*h*w doubles) receives
+ *   min over the features of fl(fl(fl(wx dx^2) + fl(wy dy^2)) + fl(wz dz^2)),   +inf when there is no feature,
+ * every fl one float64 rounding and no fused multiply-add: exactly the bits of the brute-force minimum, which the three
+ * separable passes (x, y, z; three launches, in place in dist2, no other scratch) reproduce because rounding is monotone.
+ * Extents 1 .. MSK_EDT_MAX_EXTENT per axis, spacing > 0 with its square in [1e-300, 1e300]; anything else is an error.
+ * Asynchronous; vol is not modified.                                                                                    */
+#define MSK_EDT_MAX_EXTENT 2048
+int msk_edt3d(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, const double* spacing,
+              double* dist2);
+/* *count (device, one unsigned 64-bit word, overwritten) = number of surface voxels of {vol == cls} (definition above):
+ * the capacity msk_surface_gather needs.  Asynchronous.                                                                */
+int msk_surface_count(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, unsigned long long* count);
+/* stage 2: out[0 .. min(*count, capacity)) = dist2[v] at every surface voxel v of {vol == cls}, in no particular order
+ * (the host sorts); *count (device, overwritten) = the number of surface voxels, also when it exceeds capacity -- nothing
+ * is written beyond capacity.  With dist2 = msk_edt3d of the OTHER mask's surface these are the directed squared surface
+ * distances.  Asynchronous; vol and dist2 are not modified.                                                             */
+int msk_surface_gather(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, const double* dist2, double* out,
+                       long capacity, unsigned long long* count);
 
 /* Bias gradient of a convolution that feeds a BatchNorm, from the sums msk_affine_act_bwd_reduce
  * already produced (no extra pass over dy): with batch statistics sum_v dy[v][c] is identically 0

@@ -153,6 +153,9 @@ SIGNATURES = {
     "msk_auc_pack": (_i, [_vp, _T, _vp, _vp, C.c_long, C.c_long, _vp]),
     "msk_auc_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),
     "msk_auc_counts": (_i, [_vp, _vp, C.c_long, C.c_long, _i, _vp, _sz, _vp]),
+    "msk_edt3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "msk_surface_count": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "msk_surface_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp]),
     "msk_interp_trilinear_fwd": (_i, [_vp, _T, _T]),
     "msk_interp_scratch_bytes": (_i, [_vp, _T, _T, C.POINTER(_sz)]),
     "msk_interp_trilinear_bwd": (_i, [_vp, _T, _T, _i, _vp, _sz]),

@@ -45,7 +45,8 @@ def _image_info(dataset_json, idx):
 
 
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
-             save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False):
+             save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False, surface_metrics=False,
+             surface_spacing=None):
     """auc_device (with auc_roc): the softmax scores of every volume stay on the device as sortable keys
     (utils.metric.AucScores) and the AUC comes from exact pair counts taken there, downloaded once after the loop --
     the same float as the host path, without the download of the probabilities and the host sorts.
@@ -54,7 +55,18 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     ``pred_transform`` first when given: any callable IntTensor -> IntTensor, e.g. TopkLargestConnectComponent(k=1))
     against the label on the device: confusion counts of every volume into one buffer (utils.metric.confusion_counts),
     downloaded once after the loop.  Adds miou, dice (both pooled over the set), dice_per_case (mean over volumes of the
-    class-mean Dice), acc, kappa, class_iou, class_dice to the result.  ``mdice`` stays the soft V-Net Dice of the loss."""
+    class-mean Dice), acc, kappa, class_iou, class_dice to the result.  ``mdice`` stays the soft V-Net Dice of the loss.
+
+    surface_metrics: also score the boundary of the same hard-label prediction (after ``pred_transform``, as above) per
+    volume and foreground class on the device (utils.metric.surface_metrics: exact distance transforms, only the surface
+    voxels' distances are downloaded).  Adds hd95 and assd (nanmean over the volumes of the nanmean over the classes
+    1 .. C-1), class_hd95 and class_assd (nanmean over the volumes) and surface_nan (the number of (volume, class) pairs
+    whose class has no surface in the prediction or in the label: nan, left out of the means).  ``surface_spacing``:
+    (s0, s1, s2) in the LABEL ARRAY's axis order, None = voxel units.  The dataset json's ``spacing_resample`` is not
+    accepted as a source: it exists only for datasets prepared with a resample step, is keyed by the source file (a
+    multi-volume file yields several arrays under other names), and neither the json nor the dataset records which
+    array axis it belongs to after the remaining preparation steps -- the 'xyz' of the saved NIfTI files above is an
+    assumption of this loop, not a recorded fact.  ignore_index gets no special treatment."""
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -77,6 +89,7 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     num_classes, ignore_index = eval_dataset.num_classes, getattr(eval_dataset, "ignore_index", 255)
     logits_all, label_all = [], []   # auc_roc: softmax scores and labels of the whole set on the host (core/val.py:121-131)
     auc_scores = None                # auc_roc with auc_device: the same scores as keys on the device
+    surface_cases = []               # surface_metrics: one utils.metric.surface_metrics result per volume
     with nn.fused_inference():       # one scope for the whole set: BN is folded into the conv weights once
         for it, (im, label, idx) in enumerate(loader):
             reader_cost_averager.record(time.time() - batch_start)
@@ -85,13 +98,16 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                                            transforms=eval_dataset.transforms.transforms)
             loss, per_channel_dice = loss_computation(logits, label_t, new_loss)
             loss = sum(loss)
-            if hard_metrics:
-                if counts is None:
-                    counts = metric.ConfusionCounts(pred.dev, total_iters, num_classes, ignore_index, zero=True)
+            if hard_metrics or surface_metrics:
                 hard = pred_transform(pred) if pred_transform is not None else pred
                 if isinstance(hard, tuple):     # the transform classes return (pred, label)
                     hard = hard[0]
+            if hard_metrics:
+                if counts is None:
+                    counts = metric.ConfusionCounts(pred.dev, total_iters, num_classes, ignore_index, zero=True)
                 metric.confusion_counts(hard, label_t, num_classes, ignore_index, out=counts.rows(it, len(label)))
+            if surface_metrics:
+                surface_cases.append(metric.surface_metrics(hard, label_t, num_classes, spacing=surface_spacing))
             if auc_roc:
                 lg = logits[0] if isinstance(logits, (list, tuple)) else logits
                 probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
@@ -150,6 +166,14 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         hard_infor = ("[EVAL] Hard labels: mIoU: {:.4f}, Dice: {:.4f}, Dice per case: {:.4f}, Acc: {:.4f}, Kappa: {:.4f}".format(
             miou, hdice, dice_per_case, acc, kappa),
             "[EVAL] Class IoU: \n" + str(np.round(class_iou, 4)) + "\n[EVAL] Class hard dice: \n" + str(np.round(class_dice, 4)))
+    surface_infor = None
+    if surface_metrics and surface_cases:
+        ss = metric.surface_summary(surface_cases)
+        result_dict.update(ss)
+        surface_infor = ("[EVAL] Surface ({}): HD95: {:.4f}, ASSD: {:.4f}, nan entries: {}".format(
+            "voxels" if surface_spacing is None else "spacing {}".format(tuple(float(v) for v in surface_spacing)),
+            ss["hd95"], ss["assd"], ss["surface_nan"]),
+            "[EVAL] Class HD95: \n" + str(np.round(ss["class_hd95"], 4)) + "\n[EVAL] Class ASSD: \n" + str(np.round(ss["class_assd"], 4)))
     if print_detail and local_rank == 0:
         logger.info("[EVAL] #Images: {}, Dice: {:.4f}, Loss: {:6f}".format(len(eval_dataset), mdice,
                                                                            float(np.ravel(loss_all)[0])) + auc_infor)
@@ -157,4 +181,7 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         if hard_infor is not None:
             logger.info(hard_infor[0])
             logger.info(hard_infor[1])
+        if surface_infor is not None:
+            logger.info(surface_infor[0])
+            logger.info(surface_infor[1])
     return result_dict

@@ -1,6 +1,8 @@
 """Metrics of the evaluation loop: auc_roc on the host, or for device inputs from exact pair counts taken on the device
 (auc_counts / AucScores / auc_from_counts below); the hard-label family (calculate_area, mean_iou, dice, accuracy,
-kappa) from confusion counts taken on the device (second half of this file).
+kappa) from confusion counts taken on the device (second half of this file); the boundary metrics (Hausdorff distance,
+HD95, average symmetric surface distance) from an exact squared Euclidean distance transform, on the device for device
+inputs (last part of this file: surface_mask, edt_squared, surface_distances, surface_metrics).
 
 auc_roc: area under the ROC curve of the softmax scores collected by ``core.val.evaluate(auc_roc=True)`` -- the quantity the
 reference takes from ``sklearn.metrics.roc_auc_score`` (medicalseg/utils/metric.py:64-107): binary = AUC of the class-1
@@ -441,3 +443,276 @@ def per_case(counts, num_classes, ignore_index=255):
                      ("kappa", kappa(i, p, l))):
             res[k].append(v)
     return {k: np.asarray(v, dtype=np.float64) for k, v in res.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Boundary metrics: Hausdorff distance, HD95 and average symmetric surface distance (ASSD) with medpy's conventions
+# (the reference has none), from an exact squared Euclidean distance transform.  Volumes are [D, H, W] with axes
+# (z, y, x); spacing = (sz, sy, sx) in float64, None = (1, 1, 1); wz, wy, wx = sz*sz, sy*sy, sx*sx, rounded once.
+#   surface S(M): the voxels of the boolean mask M with at least one of the six face neighbours outside M, where
+#       everything beyond the volume's edge is outside (= M & ~scipy.ndimage.binary_erosion(M));
+#   squared EDT of a feature set F at voxel v:  min over u in F of fl(fl(fl(wx dx^2) + fl(wy dy^2)) + fl(wz dz^2)),
+#       dx, dy, dz integer index differences, every fl one float64 rounding, no fused multiply-add; +inf for empty F.
+#       Rounding is monotone, so the separable evaluation (x pass: wx dx^2 of the nearest feature of the row; y pass:
+#       min over y' of gx(y') + wy (y - y')^2; the same along z) gives the same bits as the brute-force minimum;
+#   for class c with P = S(pred == c), L = S(label == c):  d2_pl = dist2_L at the voxels of P, d2_lp = dist2_P at the
+#       voxels of L, both sorted; d = sqrt(d2);  hd = max(max d_pl, max d_lp),  hd95 = np.percentile(d_pl ++ d_lp, 95),
+#       assd = (mean d_pl + mean d_lp) / 2;  all three nan when either surface is empty.
+# ignore_index gets no special treatment here: a voxel labelled ignore_index belongs to no class c != ignore_index and
+# therefore lies outside every mask (label == c), like any other value.
+# edt_squared / surface_mask on numpy arrays ARE this specification (exact, not fast); device inputs go through
+# csrc/msk_edt.hip (msk_edt3d, msk_surface_count, msk_surface_gather), which is held to the same bits.
+
+EDT_MAX_EXTENT = 2048       # MSK_EDT_MAX_EXTENT of include/msegk.h
+
+
+def _spacing_weights(spacing):
+    if spacing is None:
+        return np.ones(3, dtype=np.float64), None
+    s = np.asarray(spacing, dtype=np.float64).reshape(-1)
+    if s.shape != (3,):
+        raise ValueError("spacing must be (sz, sy, sx), got {}".format(spacing))
+    with np.errstate(over="ignore", invalid="ignore"):
+        w = s * s
+    if not (np.all(s > 0) and np.all(w >= 1e-300) and np.all(w <= 1e300)):
+        raise ValueError("spacing must be positive with its square within [1e-300, 1e300], got {}".format(spacing))
+    return w, s
+
+
+def surface_mask(mask):
+    """S(M) of a boolean [D, H, W] array: the voxels of M with a face neighbour outside M (the edge counts as outside)"""
+    m = np.asarray(mask).astype(bool)
+    if m.ndim != 3:
+        raise ValueError("expected a [D, H, W] mask, got shape {}".format(m.shape))
+    p = np.pad(m, 1, mode="constant", constant_values=False)
+    inner = (p[:-2, 1:-1, 1:-1] & p[2:, 1:-1, 1:-1] & p[1:-1, :-2, 1:-1] & p[1:-1, 2:, 1:-1] &
+             p[1:-1, 1:-1, :-2] & p[1:-1, 1:-1, 2:])
+    return m & ~inner
+
+
+def _edt_row_pass(f, w):
+    """[n, L] bool -> w * dx^2 of the nearest True of every row (one rounding), +inf for a row without one"""
+    n, L = f.shape
+    x = np.arange(L, dtype=np.int64)
+    far = np.int64(4 * L + 4)
+    left = np.maximum.accumulate(np.where(f, x, -far), axis=1)                         # nearest feature at or left of x
+    right = np.minimum.accumulate(np.where(f, x, far)[:, ::-1], axis=1)[:, ::-1]       # ... at or right of x
+    dx = np.minimum(x - left, right - x)
+    g = w * (dx * dx).astype(np.float64)
+    g[~f.any(axis=1)] = np.inf
+    return g
+
+
+def _edt_line_pass(g, w, chunk=8192):
+    """[n, L] float64 -> out[i, l] = min over l' of fl(g[i, l'] + fl(w (l - l')^2)), by brute force over the offsets;
+    an offset k is only skipped when fl(w k^2) alone is >= every running minimum of the chunk (no candidate
+    fl(g + fl(w k^2)) >= fl(w k^2) can lower any of them), which changes no bit."""
+    w = float(w)
+    out = np.array(g, dtype=np.float64, copy=True)
+    n, L = out.shape
+    live = np.flatnonzero(np.isfinite(out).any(axis=1))        # a line without a feature stays +inf
+    for a in range(0, live.size, chunk):
+        rows = live[a:a + chunk]
+        src = out[rows]
+        best = src.copy()
+        for k in range(1, L):
+            c = w * float(k * k)
+            if c >= best.max():
+                break
+            np.minimum(best[:, k:], src[:, :-k] + c, out=best[:, k:])
+            np.minimum(best[:, :-k], src[:, k:] + c, out=best[:, :-k])
+        out[rows] = best
+    return out
+
+
+def _edt_squared_host(features, spacing):
+    f = np.asarray(features).astype(bool)
+    if f.ndim != 3:
+        raise ValueError("expected a [D, H, W] feature mask, got shape {}".format(f.shape))
+    (wz, wy, wx), _ = _spacing_weights(spacing)
+    D, H, W = f.shape
+    g = _edt_row_pass(f.reshape(D * H, W), wx).reshape(D, H, W)
+    g = _edt_line_pass(g.transpose(0, 2, 1).reshape(D * W, H), wy).reshape(D, W, H).transpose(0, 2, 1)
+    g = _edt_line_pass(g.transpose(1, 2, 0).reshape(H * W, D), wz).reshape(H, W, D).transpose(2, 0, 1)
+    return np.ascontiguousarray(g)
+
+
+def _device_volume(x, what):
+    """(dev, ptr, (D, H, W)) of an int32 IntTensor [1, 1, D, H, W] / [1, D, H, W] / [D, H, W] or DeviceVolume"""
+    if getattr(x, "dtype", np.dtype(np.int32)) != np.int32:
+        raise TypeError("device volumes must be int32, got {}".format(x.dtype))
+    n, shape = _volume_shape(x)
+    if n != 1:
+        raise ValueError("{}: one volume at a time, got a batch of {}".format(what, n))
+    if max(shape) > EDT_MAX_EXTENT:
+        raise ValueError("{}: extents up to {} per axis are supported, got {}".format(what, EDT_MAX_EXTENT, shape))
+    return x.dev, x.ptr, shape
+
+
+def _c_spacing(spacing):
+    import ctypes as C
+    _, s = _spacing_weights(spacing)
+    return None if s is None else (C.c_double * 3)(*s.tolist())
+
+
+def edt_squared(x, spacing=None, cls=1, surface_only=False):
+    """Exact squared Euclidean distance transform (specification above) to the features of ``x``.
+
+    numpy input: ``x`` is the boolean feature mask [D, H, W] itself (``cls`` is not used; ``surface_only`` takes
+    surface_mask(x) first); returns a float64 array.  Device input (int32 ``IntTensor`` [1, 1, D, H, W] / [1, D, H, W]
+    or 3-D ``DeviceVolume``): the features are the voxels with ``x == cls``, or their surface with ``surface_only``;
+    one msk_edt3d call, no synchronisation; returns a float64 ``DeviceVolume`` (``numpy()``, ``free()``) holding the
+    same bits.  Extents up to EDT_MAX_EXTENT per axis on the device."""
+    if not _is_device(x):
+        f = np.asarray(x).astype(bool)
+        return _edt_squared_host(surface_mask(f) if surface_only else f, spacing)
+    import ctypes as C
+    from ..preprocess import DeviceVolume
+    dev, ptr, (d, h, w) = _device_volume(x, "edt_squared")
+    out = DeviceVolume(dev, dev.malloc(8 * d * h * w), (d, h, w), np.float64)
+    try:
+        dev.call("msk_edt3d", C.c_void_p(ptr), d, h, w, int(cls), 1 if surface_only else 0, _c_spacing(spacing),
+                 C.c_void_p(out.ptr))
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+class SurfaceDistances:
+    """The two directed multisets of SQUARED surface distances of one class, sorted ascending: ``d2_pl`` (from the
+    prediction's surface voxels to the label's surface) and ``d2_lp`` (the other way).  Metrics follow medpy and are
+    nan when either surface is empty."""
+
+    def __init__(self, d2_pl, d2_lp):
+        self.d2_pl = np.sort(np.asarray(d2_pl, dtype=np.float64).reshape(-1))
+        self.d2_lp = np.sort(np.asarray(d2_lp, dtype=np.float64).reshape(-1))
+
+    @property
+    def empty(self):
+        return self.d2_pl.size == 0 or self.d2_lp.size == 0
+
+    def distances(self):
+        """(d_pl, d_lp): the square roots, still sorted"""
+        return np.sqrt(self.d2_pl), np.sqrt(self.d2_lp)
+
+    def hd(self):
+        if self.empty:
+            return float("nan")
+        d_pl, d_lp = self.distances()
+        return float(max(d_pl[-1], d_lp[-1]))
+
+    def percentile(self, q):
+        if self.empty:
+            return float("nan")
+        return float(np.percentile(np.concatenate(self.distances()), q))
+
+    def hd95(self):
+        return self.percentile(95)
+
+    def assd(self):
+        if self.empty:
+            return float("nan")
+        d_pl, d_lp = self.distances()
+        return float((np.mean(d_pl) + np.mean(d_lp)) / 2)
+
+
+def _surface_distances_device(pred, label, cls, spacing):
+    import ctypes as C
+    dev, pp, shape = _device_volume(pred, "surface_distances")
+    dev_l, lp, shape_l = _device_volume(label, "surface_distances")
+    if dev is not dev_l:
+        raise ValueError("pred and label are on different devices")
+    if shape != shape_l:
+        raise ValueError('Shape of `pred` and `label should be equal, but there are {} and {}.'.format(
+            list(shape), list(shape_l)))
+    d, h, w = shape
+    dims = (d, h, w, int(cls))
+    sp = _c_spacing(spacing)
+    vp = C.c_void_p
+    words = dev.malloc(32)
+    dist = out_p = out_l = None
+    try:
+        dev.call("msk_surface_count", vp(pp), *dims, vp(words))
+        dev.call("msk_surface_count", vp(lp), *dims, vp(words + 8))
+        n_p, n_l = (int(v) for v in dev.d2h(words, (2,), np.uint64))
+        if n_p == 0 or n_l == 0:
+            # a metric is nan as soon as one surface is empty; the other side's distances would all be +inf
+            empty = np.zeros(0, np.float64)
+            return SurfaceDistances(empty if n_p == 0 else np.full(n_p, np.inf), empty if n_l == 0 else np.full(n_l, np.inf))
+        dist = dev.malloc(8 * d * h * w)
+        out_p, out_l = dev.malloc(8 * n_p), dev.malloc(8 * n_l)
+        dev.call("msk_edt3d", vp(lp), *dims, 1, sp, vp(dist))
+        dev.call("msk_surface_gather", vp(pp), *dims, vp(dist), vp(out_p), C.c_long(n_p), vp(words + 16))
+        dev.call("msk_edt3d", vp(pp), *dims, 1, sp, vp(dist))
+        dev.call("msk_surface_gather", vp(lp), *dims, vp(dist), vp(out_l), C.c_long(n_l), vp(words + 24))
+        d2_pl = dev.d2h(out_p, (n_p,), np.float64)
+        d2_lp = dev.d2h(out_l, (n_l,), np.float64)
+        got = tuple(int(v) for v in dev.d2h(words + 16, (2,), np.uint64))
+        if got != (n_p, n_l):
+            raise RuntimeError("surface_distances: gathered {} values, counted {}".format(got, (n_p, n_l)))
+        return SurfaceDistances(d2_pl, d2_lp)
+    finally:
+        for ptr in (words, dist, out_p, out_l):
+            if ptr:
+                dev.free(ptr)
+
+
+def surface_distances(pred, label, cls, spacing=None):
+    """The directed squared surface distances of class ``cls`` between a hard-label prediction and its label
+    (definitions above) as a ``SurfaceDistances`` (``hd()``, ``hd95()``, ``assd()``, ``percentile(q)``).
+
+    Device inputs (int32 ``IntTensor`` [1, 1, D, H, W] / [1, D, H, W], or a 3-D ``DeviceVolume``; both on one device):
+    two surface counts (one small download: an absent class ends here), then per direction one distance transform
+    and one gather on the device; only the surface voxels' values are downloaded, never a volume.  numpy inputs of
+    the same shapes run through the numpy specification.  ``ignore_index`` gets no special treatment."""
+    dev_in = (_is_device(pred), _is_device(label))
+    if dev_in[0] != dev_in[1]:
+        raise TypeError("pred and label must both be device arrays or both be host arrays")
+    if dev_in[0]:
+        return _surface_distances_device(pred, label, cls, spacing)
+    pred, label = np.asarray(pred), np.asarray(label)
+    (n, ps), (nl, ls) = _volume_shape(pred), _volume_shape(label)
+    if (n, ps) != (nl, ls):
+        raise ValueError('Shape of `pred` and `label should be equal, but there are {} and {}.'.format(
+            list((n,) + ps), list((nl,) + ls)))
+    if n != 1:
+        raise ValueError("surface_distances: one volume at a time, got a batch of {}".format(n))
+    _spacing_weights(spacing)
+    P, L = surface_mask(pred.reshape(ps) == cls), surface_mask(label.reshape(ls) == cls)
+    if not P.any() or not L.any():
+        return SurfaceDistances(np.full(int(P.sum()), np.inf), np.full(int(L.sum()), np.inf))
+    return SurfaceDistances(_edt_squared_host(L, spacing)[P], _edt_squared_host(P, spacing)[L])
+
+
+def surface_metrics(pred, label, num_classes, spacing=None, classes=None):
+    """{'hd', 'hd95', 'assd'}: float64 arrays with one entry per class of ``classes`` (None = the foreground classes
+    1 .. num_classes - 1) for one volume, nan where the class has no surface in ``pred`` or in ``label``; 'classes'
+    holds the class indices.  Inputs as in ``surface_distances``."""
+    classes = list(range(1, int(num_classes))) if classes is None else [int(c) for c in classes]
+    res = {k: np.full(len(classes), np.nan, dtype=np.float64) for k in ("hd", "hd95", "assd")}
+    for i, c in enumerate(classes):
+        sd = surface_distances(pred, label, c, spacing)
+        res["hd"][i], res["hd95"][i], res["assd"][i] = sd.hd(), sd.hd95(), sd.assd()
+    res["classes"] = np.asarray(classes, dtype=np.int64)
+    return res
+
+
+def _nanmean(a, axis=None):
+    """np.nanmean without the warning for an all-nan slice (whose mean is nan)"""
+    a = np.asarray(a, dtype=np.float64)
+    ok = ~np.isnan(a)
+    cnt = ok.sum(axis=axis)
+    tot = np.where(ok, a, 0.0).sum(axis=axis)
+    return np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan)
+
+
+def surface_summary(per_case):
+    """What evaluate(surface_metrics=True) reports from the per-case results of ``surface_metrics`` (a list of its
+    dicts, same classes): hd95 / assd = nanmean over the cases of the nanmean over the classes, class_hd95 /
+    class_assd = nanmean over the cases per class, surface_nan = nan entries of the [cases, classes] hd95 table."""
+    h = np.stack([np.asarray(r["hd95"], dtype=np.float64) for r in per_case])
+    a = np.stack([np.asarray(r["assd"], dtype=np.float64) for r in per_case])
+    return {"hd95": float(_nanmean(_nanmean(h, axis=1))), "assd": float(_nanmean(_nanmean(a, axis=1))),
+            "class_hd95": _nanmean(h, axis=0), "class_assd": _nanmean(a, axis=0),
+            "surface_nan": int(np.isnan(h).sum())}

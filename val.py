@@ -19,6 +19,8 @@ def parse_args():
                    help='With --auc_roc: keep the scores on the GPU and compute the AUC there (same value)')
     p.add_argument('--hard_metrics', dest='hard_metrics', type=bool, default=False,
                    help='Whether to report the hard-label metrics (mIoU, Dice, accuracy, kappa) of the prediction')
+    p.add_argument('--surface_metrics', dest='surface_metrics', type=bool, default=False,
+                   help='Whether to report the boundary metrics (HD95, ASSD; in voxels) of the hard-label prediction')
     return p.parse_args()
 
 
@@ -37,7 +39,8 @@ def main(args):
         load_entire_model(model, args.model_path)
         logger.info('Loaded trained params of model successfully')
     print(evaluate(model, val_dataset, cfg.loss, num_workers=args.num_workers, print_detail=args.print_detail,
-                   auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device))
+                   auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device,
+                   surface_metrics=args.surface_metrics))
 
 
 if __name__ == '__main__':
