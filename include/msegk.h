@@ -414,6 +414,19 @@ int msk_argmax_c(msk_ctx* ctx, msk_tensor x, int32_t* out);
 /* out[v][c] = softmax over c of x[v][:]  -- F.softmax(logits, axis=1) of the AUC path of evaluate (core/val.py:121-123)  */
 int msk_softmax_c(msk_ctx* ctx, msk_tensor x, msk_tensor out);
 
+/* ---- test-time augmentation (core/infer.py aug_inference) ------------------- */
+/* dst = src mirrored along the axes of mask (bit 0 = D, bit 1 = H, bit 2 = W; per batch item, any c, any ld >= c), out of
+ * place, in one pass: np.flip bit for bit.  mask 0 copies.                                                           */
+int msk_flip_axes(msk_ctx* ctx, msk_tensor src, msk_tensor dst, int mask);
+/* acc[v][c] = first ? p : acc[v][c] + p, p = msk_softmax_c's value (the same operations in the same order) of the logits
+ * at the voxel v is mirrored to by mask: one pass of a flip-averaged prediction without the mirrored copy and the
+ * probabilities in between.  The addition is an fp32 addition of its own, never fused with the softmax's multiply.    */
+int msk_tta_accumulate(msk_ctx* ctx, msk_tensor logits, int mask, msk_tensor acc, int first);
+/* probs[v][c] = acc[v][c] * (1.f / passes) (one fp32 multiply), pred[v] = argmax over c of acc[v][:] (first maximum wins,
+ * msk_argmax_c).  probs.p and pred may each be null.  All three: asynchronous on the context stream, no atomics,
+ * nothing data-dependent can fail; shape mismatch, mask outside 0..7 and passes < 1 are argument errors.             */
+int msk_tta_finish(msk_ctx* ctx, msk_tensor acc, int passes, msk_tensor probs, int32_t* pred);
+
 /* ---- loss ------------------------------------------------------------------ */
 /* losses/loss_utils.py:31-40 class_weights: w_c = sum(1-softmax_c)/sum(softmax_c) */
 int msk_class_weights(msk_ctx* ctx, msk_tensor logits, float* weights);

@@ -127,6 +127,9 @@ SIGNATURES = {
     "msk_channel_sum": (_i, [_vp, _T, _vp, _i]),
     "msk_argmax_c": (_i, [_vp, _T, _vp]),
     "msk_softmax_c": (_i, [_vp, _T, _T]),
+    "msk_flip_axes": (_i, [_vp, _T, _T, _i]),
+    "msk_tta_accumulate": (_i, [_vp, _T, _i, _T, _i]),
+    "msk_tta_finish": (_i, [_vp, _T, _i, _T, _vp]),
     "msk_class_weights": (_i, [_vp, _T, _vp]),
     "msk_loss_fwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _vp]),
     "msk_loss_bwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _f, _f, _T]),

@@ -46,8 +46,13 @@ def _image_info(dataset_json, idx):
 
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
              save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False, surface_metrics=False,
-             surface_spacing=None):
-    """auc_device (with auc_roc): the softmax scores of every volume stay on the device as sortable keys
+             surface_spacing=None, aug_eval=False, scales=1.0, flip_axes=()):
+    """aug_eval: the hard-label prediction (what pred_transform, hard_metrics, surface_metrics and the saved arrays see) and
+    the AUC scores come from ``infer.aug_inference(scales=scales, flip_axes=flip_axes)``: the mean softmax over the mirrored
+    (flip_axes: 0/1/2 = D/H/W, every subset) and rescaled passes and its argmax, in place of the single pass's.  ``mdice``
+    and the loss stay those of the plain pass (its logits come back from the same call), so ``scales`` must contain 1.0.
+
+    auc_device (with auc_roc): the softmax scores of every volume stay on the device as sortable keys
     (utils.metric.AucScores) and the AUC comes from exact pair counts taken there, downloaded once after the loop --
     the same float as the host path, without the download of the probabilities and the host sorts.
 
@@ -67,6 +72,9 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     multi-volume file yields several arrays under other names), and neither the json nor the dataset records which
     array axis it belongs to after the remaining preparation steps -- the 'xyz' of the saved NIfTI files above is an
     assumption of this loop, not a recorded fact.  ignore_index gets no special treatment."""
+    if aug_eval and (1.0, 0) not in infer.tta_passes(scales, flip_axes):
+        raise ValueError("evaluate(aug_eval=True): scales must contain 1.0 (mdice and the loss are the plain pass's), got %r"
+                         % (scales,))
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -94,8 +102,16 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         for it, (im, label, idx) in enumerate(loader):
             reader_cost_averager.record(time.time() - batch_start)
             label_t = to_tensor(label.astype('int32'))
-            pred, logits = infer.inference(model, to_tensor(im), ori_shape=label.shape[-3:],
-                                           transforms=eval_dataset.transforms.transforms)
+            if aug_eval:
+                pred, mean_probs, logits = infer.aug_inference(model, to_tensor(im), ori_shape=label.shape[-3:],
+                                                               transforms=eval_dataset.transforms.transforms,
+                                                               scales=scales, flip_axes=flip_axes, with_plain=True)
+                if tuple(label.shape[-3:]) != tuple(logits.shape[2:]):      # as inference() does before the loss
+                    logits = infer.reverse_transform(logits, label.shape[-3:], eval_dataset.transforms.transforms,
+                                                     mode='bilinear')
+            else:
+                pred, logits = infer.inference(model, to_tensor(im), ori_shape=label.shape[-3:],
+                                               transforms=eval_dataset.transforms.transforms)
             loss, per_channel_dice = loss_computation(logits, label_t, new_loss)
             loss = sum(loss)
             if hard_metrics or surface_metrics:
@@ -110,8 +126,11 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                 surface_cases.append(metric.surface_metrics(hard, label_t, num_classes, spacing=surface_spacing))
             if auc_roc:
                 lg = logits[0] if isinstance(logits, (list, tuple)) else logits
-                probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
-                lg.dev.call("msk_softmax_c", lg.msk(), probs.msk())       # F.softmax(logits, axis=1) on the device
+                if aug_eval:
+                    probs = mean_probs                                        # the mean softmax over the passes
+                else:
+                    probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
+                    lg.dev.call("msk_softmax_c", lg.msk(), probs.msk())       # F.softmax(logits, axis=1) on the device
                 if auc_device:
                     if auc_scores is None:      # room for the whole set at the size of the first volume; grows otherwise
                         auc_scores = metric.AucScores(lg.dev, num_classes, total_iters * probs.voxels)

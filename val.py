@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description='Model evaluation')
     p.add_argument("--config", dest="cfg", help="The config file.", default=None, type=str)
     p.add_argument('--model_path', dest='model_path', help='The path of model for evaluation', type=str, default=None)
@@ -21,7 +21,13 @@ def parse_args():
                    help='Whether to report the hard-label metrics (mIoU, Dice, accuracy, kappa) of the prediction')
     p.add_argument('--surface_metrics', dest='surface_metrics', type=bool, default=False,
                    help='Whether to report the boundary metrics (HD95, ASSD; in voxels) of the hard-label prediction')
-    return p.parse_args()
+    p.add_argument('--aug_eval', dest='aug_eval', type=bool, default=False,
+                   help='Whether to average the softmax over mirrored / rescaled passes (test-time augmentation)')
+    p.add_argument('--scales', dest='scales', nargs='+', type=float, default=1.0,
+                   help='With --aug_eval: scales of the passes; must contain 1.0')
+    p.add_argument('--flip_axes', dest='flip_axes', nargs='*', type=int, default=(),
+                   help='With --aug_eval: axes to mirror, 0 1 2 = D H W; every subset is one pass')
+    return p.parse_args(argv)
 
 
 def main(args):
@@ -40,7 +46,8 @@ def main(args):
         logger.info('Loaded trained params of model successfully')
     print(evaluate(model, val_dataset, cfg.loss, num_workers=args.num_workers, print_detail=args.print_detail,
                    auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device,
-                   surface_metrics=args.surface_metrics))
+                   surface_metrics=args.surface_metrics, aug_eval=args.aug_eval, scales=args.scales,
+                   flip_axes=args.flip_axes))
 
 
 if __name__ == '__main__':
