@@ -126,6 +126,7 @@ int msk_prof_report(msk_ctx* ctx, char* buf, int buflen, int* len);
  *     scaled by a power of two derived on the device, forward activations must stay below 3000 in magnitude);
  *   "bwd_fuse" -1|0|1|2 (msk_conv3d_bwd_bnact: auto | three calls | one dual transform | one transform per stream),
  *     "foldn_wgs" (workgroups per CU targeted by the D segmentation of conv_foldn_k, 0 = 2);
+ *     "tk_join" 1|0 (msk_conv3d_bwd_bnact_join: 1 = the join backward runs in the data-gradient kernel's epilogue, 0 = it declines);
  *     "wbf_pad_min_voxels" (smallest 5^3 problem whose channel counts are not multiples of 32 that is run through the
  *         16-bit pipeline on a zero-padded copy, default 2^18);
  *     "wbf_tin_groups" (workgroups below which the pipeline's transform kernels cut their W tiles into chunks, -1 = 8 per CU, 0 = never);
@@ -287,6 +288,27 @@ int msk_conv3d_bwd_bnact_acc(msk_ctx* ctx, msk_conv_desc cd, msk_tensor x, const
                              msk_tensor dout, const float* sums_total, double M_total, msk_tensor dy_scratch, msk_tensor dx,
                              int dx_accumulate, float* dw, int dw_accumulate, const void* xform, void* ybuf, const float* maxes,
                              msk_tensor dx_old, msk_tensor dx_lo, msk_tensor dx_hi, int* split_done);
+/* Backward of a unit conv5^3 -> BatchNorm(batch statistics) -> PReLU with <= 4 output channels whose 32-channel input x is the
+ * output of a residual join fused with ITS unit, out = prelu(prelu(jscale * jy + jshift, jalpha_inner) + jres, jalpha_outer)
+ * (out_tr.conv1 behind up_tr32's join, vnet.py:154,173), together with that join's backward, in one call:
+ *     dy = msk_affine_act_bwd_apply_amax(y, ..., dout, sums_total, M_total, bn_mode 1) (dy_amax nullable),
+ *     dw (+)= sum dy * x   (msk_conv3d_wgrad_ex3: xform / x_amax nullable),
+ *     msk_add_act_join_bwd_pg(jy, ..., dout = conv^T(dy, w), da, dres, ...) with the same trailing arguments --
+ * evaluated in the epilogue of the data-gradient kernel, so the join's output gradient is never stored.  da is bitwise what the
+ * separate calls give; unit_sums and the parameter gradients differ by their summation order.  unit_sums needs 4*C floats
+ * (C = x.c): [0..3C) = sum du, sum du*xhat, d alpha_inner, and the merge also stores the join's slope sum in [3C..4C).
+ * dres.p NULL: the second operand's gradient is not written (it equals da: msk_conv3d_bwd_bnact_acc's dx_old).
+ * Returns 0 = done, 1 = not eligible (NOTHING was launched: use the separate calls) -- an accumulate flag set, option "tk_join" 0, "conv_split" != 2,
+ * a forced "conv_impl", x.c != 32, tensors that are not float4-aligned, volumes below 4 x 8 x 12.                          */
+int msk_conv3d_bwd_bnact_join(msk_ctx* ctx, msk_conv_desc cd, msk_tensor x, const float* w, msk_tensor y, const float* scale,
+                              const float* shift, const float* alpha /*nullable*/, const float* mean, const float* invstd,
+                              const float* gamma, msk_tensor dout, const float* sums_total, double M_total, msk_tensor dy,
+                              float* dy_amax /*nullable*/, float* dw, int dw_accumulate, const void* xform /*nullable*/,
+                              const float* x_amax /*nullable*/, msk_tensor jy, const float* jscale, const float* jshift,
+                              const float* jalpha_inner, msk_tensor jres, const float* jalpha_outer, const float* jmean,
+                              const float* jinvstd, msk_tensor da, int da_accumulate, msk_tensor dres /*p nullable*/,
+                              int dres_accumulate, float* dalpha_outer, float* unit_sums, float* maxes, int clear_maxes,
+                              float* unit_dgamma /*nullable*/, float* unit_dbeta /*nullable*/, float* unit_dalpha /*nullable*/);
 /* Backward of an up-convolution unit  convT -> BatchNorm(batch statistics) -> PReLU  (UpTransition.up_conv / bn1 / relu1,
  * vnet.py:133-150; autograd of core/train.py:139) behind its reduce pass, in one call:
  *     dx (+)= convT^T(dy, w),  dw (+)= sum x * dy,   dy = msk_affine_act_bwd_apply(y, ..., dout, sums_total, M_total, bn_mode 1)

@@ -98,6 +98,8 @@ SIGNATURES = {
     "msk_conv3d_bwd_bnact_split": (_i, [_vp, _CD, _T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _vp, _T, _vp, _d, _T, _T, _i, _vp, _i, _vp, _vp, _vp, _T, _T, C.POINTER(_i)]),
     "msk_conv3d_bwd_bnact_acc": (_i, [_vp, _CD, _T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _vp, _T, _vp, _d, _T, _T, _i, _vp, _i, _vp, _vp, _vp, _T, _T, _T, C.POINTER(_i)]),
     "msk_conv3d_bwd_inact": (_i, [_vp, _CD, _T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _i, _T, _vp, _i, _d, _T, _i, _vp, _i, _vp, _vp, _vp]),
+    "msk_conv3d_bwd_bnact_join": (_i, [_vp, _CD, _T, _vp, _T, _vp, _vp, _vp, _vp, _vp, _vp, _T, _vp, _d, _T, _vp, _vp, _i, _vp, _vp,
+                                       _T, _vp, _vp, _vp, _T, _vp, _vp, _vp, _T, _i, _T, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "msk_conv3d_bwd_bnact_c1": (_i, [_vp, _CD, _T, _T, _vp, _vp, _vp, _vp, _vp, _T, _T, _vp, _d, _vp, _i]),
     "msk_conv3d_dgrad": (_i, [_vp, _CD, _T, _vp, _T, _i]),
     "msk_conv3d_dgrad_ex": (_i, [_vp, _CD, _T, _vp, _T, _i, _vp]),
@@ -212,6 +214,7 @@ def _missing(name):
     def stub(*args, **kwargs):
         raise MskError(f"{name} is not exported by {LIB_PATH}: rebuild it with ./build.sh")
     stub.__name__ = name
+    stub.missing = True      # for callers that have an equivalent sequence of older entry points
     return stub
 
 

@@ -153,6 +153,7 @@ struct msk_ctx {
   bool host_transport = false;   // env MSEGK_DP_TRANSPORT=host: collectives through host staging + TCP (single-GPU test tier)
   std::vector<int> host_fds;
   int rank = 0, world = 1;
+  int tk_join = 1;   // option "tk_join": msk_conv3d_bwd_bnact_join may run the join backward in the epilogue of conv_tk_h2_k; 0 = it declines (A/B, tests)
   int num_cu = 256;
 };
 
@@ -182,6 +183,11 @@ void msk_small_pack_freed(msk_ctx* ctx, const void* p, size_t bytes);
 int msk_small_prepack(msk_ctx* ctx, const void* p, size_t bytes);        // p == nullptr: every stale row in use
 void msk_small_pack_free(msk_ctx* ctx);
 int msk_dp_wait_impl(msk_ctx* ctx);
+// merge of the [nb][4][C] partial sums of a join backward fused with its unit (msk_elementwise.hip: the merge launch of
+// msk_add_act_join_bwd_pg): all four quantities are stored to unit_sums, which needs 4*C floats; 0..2 are also added to the
+// (nullable) parameter gradients, 3 to dalpha
+int msk_join_sums_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* unit_sums, float* u_dbeta, float* u_dgamma,
+                        float* u_dalpha, float* dalpha);
 
 // Redirect launches of the enclosed scope to the side stream (with its own scratch) after making
 // it wait for everything enqueued so far on the main stream.

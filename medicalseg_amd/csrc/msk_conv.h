@@ -87,7 +87,25 @@ int msk_gconv_gather_mfma(msk_ctx* ctx, const GConv& g, const float* w_canon, in
 // 'same' 5^3 conv with <= 4 reduction channels: (tap, channel) pairs enumerated tightly along K (msk_conv_tightk.hip)
 int msk_gconv_halo_tightk(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap);
 // the same class (CK <= 4 -> 32 channels) with fp16 two-piece operands, kd folded into K, marching along D (msk_conv_tightk.hip)
-int msk_gconv_tk_h2(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap);
+int msk_gconv_tk_h2(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap, struct TKJoin* join = nullptr);
+// ... with `join` (msk_conv3d_bwd_bnact_join): dst is not the convolution's output but the first-operand gradient of the residual
+// join out = prelu(prelu(scale * x + shift, alpha_in) + b, alpha) whose output gradient the convolution produces -- that gradient
+// stays in registers.  The kernel leaves one row of partial sums per workgroup (partial / nb, sums_merge_k's layout: sum du,
+// sum du * xhat, d alpha_in, d alpha) and folds max |du|, max |xhat| into maxes (cleared by the caller).  Declines (0, nothing
+// launched) an accumulating problem, tensors that are not float4-aligned and option "tk_join" 0.
+struct TKJoin {
+  const float* x;   // the unit's pre-BatchNorm output
+  int xld;
+  const float* b;   // second operand of the join
+  int bld;
+  float* db;        // the second operand's gradient (a copy of the first's), or null: not written
+  int dbld;
+  const float *scale, *shift, *alpha_in, *alpha, *mean, *invstd;   // per channel [32]
+  float* maxes;
+  const float* partial;   // out: [nb][4][32] in the context's scratch
+  int nb;
+};
+bool msk_gconv_tk_h2_accepts(const msk_ctx* ctx, const GConv& g, const struct TKJoin* join);   // its eligibility tests, nothing launched
 // 'same' 5^3 conv with ONE input channel (in_tr.conv1) on the fp32 matrix pipe, weights and tap offsets in registers (msk_conv_c1.hip)
 int msk_gconv_c1_mfma(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap);
 // the same class (and 3^3 with <= 32 output channels) on the 16-bit matrix pipe with fp16 operand pieces (msk_conv_c1.hip)

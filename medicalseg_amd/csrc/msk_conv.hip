@@ -1753,6 +1753,60 @@ int msk_conv3d_bwd_bnact_acc(msk_ctx* ctx, msk_conv_desc cd, msk_tensor x, const
   return rc;
 }
 
+// Backward of the unit conv -> BatchNorm -> PReLU whose INPUT is the output of a residual join fused with its unit (out_tr.conv1
+// behind up_tr32, vnet.py:154,173), and that join's backward, in one call: dy = msk_affine_act_bwd_apply_amax(...), the weight
+// gradient (msk_conv3d_wgrad_ex3), and the data gradient conv^T(dy, w) evaluated by conv_tk_h2_k<JOIN>, whose epilogue runs
+// msk_add_act_join_bwd_pg (second gradient not written) on its accumulators: the join's output gradient never reaches HBM and da
+// (and dres, when given) is bitwise what the separate calls give; the sums differ by their summation order.  Returns 0 = done, 1 = not eligible
+// (NOTHING was launched: the caller runs the separate calls), < 0 error.
+int msk_conv3d_bwd_bnact_join(msk_ctx* ctx, msk_conv_desc cd, msk_tensor x, const float* w, msk_tensor y, const float* scale,
+                              const float* shift, const float* alpha, const float* mean, const float* invstd, const float* gamma,
+                              msk_tensor dout, const float* sums_total, double M_total, msk_tensor dy, float* dy_amax, float* dw,
+                              int dw_accumulate, const void* xform, const float* x_amax, msk_tensor jy, const float* jscale,
+                              const float* jshift, const float* jalpha_inner, msk_tensor jres, const float* jalpha_outer,
+                              const float* jmean, const float* jinvstd, msk_tensor da, int da_accumulate, msk_tensor dres,
+                              int dres_accumulate, float* dalpha_outer, float* unit_sums, float* maxes, int clear_maxes,
+                              float* unit_dgamma, float* unit_dbeta, float* unit_dalpha) {
+  if (check_conv_shapes(ctx, cd, x, y, false) != 0) return -1;
+  MSK_REQUIRE(ctx, scale && shift && mean && invstd && sums_total && M_total > 0 && w && dw, "training-mode BatchNorm coefficients required");
+  MSK_REQUIRE(ctx, dy.p && dy.n == y.n && dy.d == y.d && dy.h == y.h && dy.w == y.w && dy.c == y.c, "dy must match y");
+  MSK_REQUIRE(ctx, jscale && jshift && jalpha_inner && jalpha_outer && jmean && jinvstd && dalpha_outer && unit_sums && maxes,
+              "the join's coefficients, statistics, sums and maxima buffers");
+  const bool same = jy.n == x.n && jy.d == x.d && jy.h == x.h && jy.w == x.w && jy.c == x.c && jres.n == x.n && jres.d == x.d &&
+                    jres.h == x.h && jres.w == x.w && jres.c == x.c && da.n == x.n && da.d == x.d && da.h == x.h && da.w == x.w &&
+                    da.c == x.c && jy.p && jres.p && da.p;
+  MSK_REQUIRE(ctx, same, "the join's tensors must have the shape of x");
+  MSK_REQUIRE(ctx, !dres.p || (dres.n == x.n && dres.d == x.d && dres.h == x.h && dres.w == x.w && dres.c == x.c), "dres must have the shape of x");
+  if (ctx->conv_impl != 0 || x.c != 32 || da_accumulate || (dres.p && dres_accumulate)) return 1;
+  GConv g{};
+  g.src = (const float*)dy.p; g.sld = dy.ld; g.dst = (float*)da.p; g.dld = da.ld;
+  g.N = x.n; g.SD = dy.d; g.SH = dy.h; g.SW = dy.w; g.DD = x.d; g.DH = x.h; g.DW = x.w;
+  g.CK = dy.c; g.CN = x.c;
+  g.kd = cd.kd; g.kh = cd.kh; g.kw = cd.kw; g.sd = cd.sd; g.sh = cd.sh; g.sw = cd.sw;
+  g.pd = cd.pd; g.ph = cd.ph; g.pw = cd.pw;
+  g.transposed = 1; g.bias = nullptr; g.accumulate = 0; g.flip = 1;
+  g.w_persistent = true;
+  g.in_amax = dy_amax;
+  TKJoin j{};
+  j.x = (const float*)jy.p; j.xld = jy.ld; j.b = (const float*)jres.p; j.bld = jres.ld;
+  j.scale = jscale; j.shift = jshift; j.alpha_in = jalpha_inner; j.alpha = jalpha_outer; j.mean = jmean; j.invstd = jinvstd;
+  j.maxes = maxes;
+  j.db = (float*)dres.p; j.dbld = dres.ld;
+  const size_t per = (size_t)x.d * x.h * x.w * (x.ld > da.ld ? x.ld : da.ld) * sizeof(float);
+  if (per > 0 && (size_t)x.n > kChunkBytes / per) return 1;   // chunked batches: the plain path
+  if ((size_t)x.n * x.d * x.h * x.w >= (1ull << 31) / 64) return 1;   // 32-bit voxel indices in the kernel's epilogue
+  if (!msk_gconv_tk_h2_accepts(ctx, g, &j)) return 1;
+  if (int rc = msk_affine_act_bwd_apply_amax(ctx, y, scale, shift, msk_tensor{}, alpha, mean, invstd, gamma, dout, sums_total, M_total, 1,
+                                             dy, msk_tensor{}, 0, dy_amax))
+    return rc;
+  if (int rc = conv3d_wgrad_impl(ctx, cd, x, dy, dw, nullptr, dw_accumulate, xform, dy_amax, x_amax)) return rc;
+  if (clear_maxes) MSK_CHECK_HIP(ctx, hipMemsetAsync(maxes, 0, 2 * kWbfAmaxWays * sizeof(float), ctx->stream));
+  const int r = msk_gconv_tk_h2(ctx, g, w, dy.c, x.c, 0, &j);
+  if (r < 0) return r;
+  if (r == 0) return msk_fail(ctx, __FILE__, __LINE__, "msk_conv3d_bwd_bnact_join", "the data-gradient kernel declined a problem its plan accepted");
+  return msk_join_sums_merge(ctx, j.partial, j.nb, x.c, unit_sums, unit_dbeta, unit_dgamma, unit_dalpha, dalpha_outer);
+}
+
 int msk_conv3d_bwd_inact(msk_ctx* ctx, msk_conv_desc cd, msk_tensor x, const float* w, msk_tensor y, const float* scale,
                          const float* shift, const float* alpha, const float* mean, const float* invstd, int coef_stride,
                          msk_tensor dout, const float* sums, int sums_stride, double M_sample, msk_tensor dx, int dx_accumulate,

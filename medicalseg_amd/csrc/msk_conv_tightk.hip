@@ -190,6 +190,17 @@ struct TKH2Args {
   int tiles_h, tiles_w, segs, seg_len, nblk;
   const float* x_amax;
   const float* w_amax;
+  // JOIN (conv_tk_h2_k<true>): dst receives the first-operand gradient of the residual join whose output gradient this
+  // convolution produces, out = prelu(prelu(scale * jx + shift, alpha_in) + jb, alpha) -- see the kernel
+  const float* jx;
+  int jxld;
+  const float* jb;
+  int jbld;
+  float* jdb;             // second-operand gradient (= da), or null: its consumer reads da instead
+  int jdbld;
+  const float* jcoef[6];  // per channel [32]: scale, shift, alpha_in, alpha, mean, invstd
+  float* partial;         // [nblk][4][32]: sum du, sum du * xhat, d alpha_in, d alpha (sums_merge_k's layout)
+  unsigned* maxes;        // two amax arrays: max |du|, max |xhat|
 };
 
 // Round 4: DENSE K.  A "unit" is the (<= 4)-channel vector of one voxel of one plane = 4 of the 32 K slots of
@@ -223,11 +234,24 @@ pack_tkh2_weights_k(const float* __restrict__ w, int A, int B, int swap, int fli
   }
 }
 
+// JOIN (round 12): the convolution's output is the gradient `dout` of a residual join out = prelu(a + b), a = prelu(scale * x + shift)
+// (the up-transition in front of out_tr: AddAct with its unit).  Instead of storing dout, the epilogue of every plane runs that
+// join's backward on the accumulators (MODE 2 of affine_act_bwd_reduce_v4_k, same expressions in the same order: da is bitwise
+// what the two kernels gave) -- dout never reaches HBM.  The four per-channel sums and the two maxima run along the march in
+// registers; one partial row per workgroup, merged by sums_merge_k (fixed order: reproducible).
+// A "chunk" is one row r of one channel tile nt (a float4 of x and of b per lane).  kTKJoinPF chunks are loaded in front of the
+// plane's matrix steps (next to stage_load), the others behind them, kTKJoinAhead chunks ahead of the one being evaluated.
+#ifndef TK_JOIN_PF
+#define TK_JOIN_PF 1   // 2 and more spill under __launch_bounds__(256, 3): the 34 running sums stay in registers through the matrix steps
+#endif
+constexpr int kTKJoinPF = TK_JOIN_PF, kTKJoinAhead = 2;
+template <bool JOIN>
 __global__ void __launch_bounds__(256, 3)
 conv_tk_h2_k(TKH2Args a) {
   constexpr int TH = 16, TW = 16, HH = TH + 4, HW = TW + 4, NV = HH * HW;  // 20 x 20 = 400 voxels per plane
   constexpr int RING = 8, SLOT = 2 * NV;                                    // 8-byte units per ring slot: [piece][voxel]
-  __shared__ uint2 lds[RING * SLOT + 2];                                    // + one zero unit for the padding lanes
+  constexpr int JC = RING * SLOT + 2;                                       // JOIN: the six coefficient rows behind the ring
+  __shared__ uint2 lds[RING * SLOT + 2 + (JOIN ? 6 * 32 / 2 : 0)];          // + one zero unit for the padding lanes
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 15, lk = lane >> 4;
   int t = xcd_remap_tk(blockIdx.x, a.nblk);
   const int twi = t % a.tiles_w;
@@ -289,6 +313,79 @@ conv_tk_h2_k(TKH2Args a) {
   f32x4 acc[4][2];  // [row of the wave][output-channel tile]
   const int steps = (d_end - d_begin) + 4;
   float pre[2][4];
+  // JOIN: the lane's 8 channels are 16 nt + 4 lk + (0..3); running sums [quantity][nt][e] and maxima over the whole march
+  float js[4][2][4];
+  float jm_du = 0.f, jm_xh = 0.f;
+  int joff[4];       // voxel index of the lane's position in row r of plane 0, or -1 outside the volume
+  float4 jx[8], jb[8];   // chunk k = 4 nt + r
+  if constexpr (JOIN) {
+    float* jc = reinterpret_cast<float*>(lds + JC);
+    if (tid < 6 * 32) jc[tid] = a.jcoef[tid >> 5][tid & 31];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) js[q][nt][e] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int gh = h0 + 4 * wave + r, gw = w0 + li;
+      joff[r] = (gh < a.H && gw < a.W) ? ((n * a.D) * a.H + gh) * a.W + gw : -1;
+    }
+  }
+  const int jplane = a.H * a.W;
+  auto join_load = [&](int d, int k) {
+    const int r = k & 3, nt = k >> 2;
+    jx[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    jb[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+#ifndef TK_JOIN_NO_LOADS   // timing probe only (wrong results): the epilogue without its x / b loads
+    if (joff[r] >= 0) {
+      const long v = joff[r] + d * jplane;
+      jx[k] = *reinterpret_cast<const float4*>(a.jx + v * a.jxld + 16 * nt + 4 * lk);
+      jb[k] = *reinterpret_cast<const float4*>(a.jb + v * a.jbld + 16 * nt + 4 * lk);
+    }
+#endif
+  };
+  // one chunk: the join backward of affine_act_bwd_reduce_v4_k<2> per element, da stored through dst / dld
+  auto join_chunk = [&](int d, int k) {
+    const int r = k & 3, nt = k >> 2;
+    if (joff[r] < 0) return;
+    const float4* jc4 = reinterpret_cast<const float4*>(lds + JC);
+    const float4 c0 = jc4[0 * 8 + 4 * nt + lk], c1 = jc4[1 * 8 + 4 * nt + lk], c2 = jc4[2 * 8 + 4 * nt + lk];
+    const float4 c3 = jc4[3 * 8 + 4 * nt + lk], c4 = jc4[4 * 8 + 4 * nt + lk], c5 = jc4[5 * 8 + 4 * nt + lk];
+    const float sc[4] = {c0.x, c0.y, c0.z, c0.w}, sf[4] = {c1.x, c1.y, c1.z, c1.w}, ai[4] = {c2.x, c2.y, c2.z, c2.w};
+    const float al[4] = {c3.x, c3.y, c3.z, c3.w}, mu[4] = {c4.x, c4.y, c4.z, c4.w}, is[4] = {c5.x, c5.y, c5.z, c5.w};
+    const float xv[4] = {jx[k].x, jx[k].y, jx[k].z, jx[k].w}, rv[4] = {jb[k].x, jb[k].y, jb[k].z, jb[k].w};
+    float du[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dv = acc[r][nt][j] * osc;
+      float t = fmaf(xv[j], sc[j], sf[j]);
+      const float tin = t;
+      if (!(t > 0.f)) t *= ai[j];
+      const float u = t + rv[j];
+      t = tin;  // pre-activation of the unit
+      float g = dv;
+      if (!(u > 0.f)) {
+        g = al[j] * dv;
+        js[3][nt][j] = fmaf(dv, u, js[3][nt][j]);
+      }
+      du[j] = g;
+      float gu = g;  // gradient w.r.t. the BatchNorm output of the unit
+      if (!(t > 0.f)) {
+        gu = g * ai[j];
+        js[2][nt][j] = fmaf(g, fmaf(xv[j], sc[j], sf[j]), js[2][nt][j]);
+      }
+      const float xh = (xv[j] - mu[j]) * is[j];
+      js[0][nt][j] += gu;
+      js[1][nt][j] = fmaf(gu, xh, js[1][nt][j]);
+      jm_du = fmaxf(jm_du, fabsf(gu));
+      jm_xh = fmaxf(jm_xh, fabsf(xh));
+    }
+    const long v = joff[r] + d * jplane;
+    *reinterpret_cast<float4*>(a.dst + v * a.dld + 16 * nt + 4 * lk) = make_float4(du[0], du[1], du[2], du[3]);
+    if (a.jdb) *reinterpret_cast<float4*>(a.jdb + v * a.jdbld + 16 * nt + 4 * lk) = make_float4(du[0], du[1], du[2], du[3]);   // (uniform)
+  };
   // planes d_begin-2 .. d_begin+2 first, then one new plane (d + 3: a sixth slot of the ring of eight) per output plane
 #pragma unroll 1
   for (int s = 0; s < 5; ++s) {
@@ -300,6 +397,10 @@ conv_tk_h2_k(TKH2Args a) {
   for (int s = 4; s < steps; ++s) {
     const int d = d_begin + s - 4;  // output plane: needs planes d-2 .. d+2
     stage_load(d + 3, pre);         // in flight during this plane's MFMAs
+    if constexpr (JOIN) {
+#pragma unroll
+      for (int k = 0; k < kTKJoinPF; ++k) join_load(d, k);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -351,7 +452,16 @@ conv_tk_h2_k(TKH2Args a) {
           acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(tk_f16x8, wf[nt][0]), __builtin_bit_cast(tk_f16x8, xh[r]), acc[r][nt], 0, 0, 0);
     }
     // D[row = output channel 16 nt + 4 lk + e][col = position li]
-    if (d < d_end) {
+    if constexpr (JOIN) {
+#pragma unroll
+      for (int k = kTKJoinPF; k < kTKJoinPF + kTKJoinAhead && k < 8; ++k) join_load(d, k);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (k >= kTKJoinPF && k + kTKJoinAhead < 8) join_load(d, k + kTKJoinAhead);
+        join_chunk(d, k);
+        __builtin_amdgcn_sched_barrier(0);   // keeps the later chunks' loads (and their registers) behind this one
+      }
+    } else if (d < d_end) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int gh = h0 + 4 * wave + r, gw = w0 + li;
@@ -373,17 +483,50 @@ conv_tk_h2_k(TKH2Args a) {
     stage_store(d + 3, pre);   // slot (d + 3) & 7 held plane d - 5: its last readers passed two barriers ago
     __syncthreads();
   }
+  if constexpr (JOIN) {
+    // the 16 lanes li of a lane group hold the same channels: butterfly over them, then the four waves through the (free) ring
+    float* red = reinterpret_cast<float*>(lds);   // [wave][quantity][channel]
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v = js[q][nt][e];
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+          if (li == 0) red[(wave * 4 + q) * 32 + 16 * nt + 4 * lk + e] = v;
+        }
+    __syncthreads();
+    if (tid < 4 * 32) {
+      const float v = ((red[tid] + red[128 + tid]) + red[256 + tid]) + red[384 + tid];
+      a.partial[(long)blockIdx.x * 128 + tid] = v;
+    }
+    block_atomic_max(a.maxes, jm_du);
+    block_atomic_max(a.maxes + kWbfAmaxWays, jm_xh);
+  }
 }
 
 }  // namespace
 
-int msk_gconv_tk_h2(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap) {
-  if (ctx->conv_split != 2 || ctx->conv_impl == 25) return 0;  // 25 = A/B: the fp32-MFMA tight-K kernel
-  if (!(g.kd == 5 && g.kh == 5 && g.kw == 5 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 2 && g.ph == 2 && g.pw == 2)) return 0;
-  if (!(g.SD == g.DD && g.SH == g.DH && g.SW == g.DW)) return 0;
-  if (g.CK < 1 || g.CK > 4 || g.CN != 32 || g.bias || g.prelu) return 0;
-  if (g.DW < 12 || g.DH < 8 || g.DD < 4) return 0;
-  if (g.dld % 4 || (((uintptr_t)g.dst) & 15)) return 0;
+bool msk_gconv_tk_h2_accepts(const msk_ctx* ctx, const GConv& g, const TKJoin* join) {
+  if (ctx->conv_split != 2 || ctx->conv_impl == 25) return false;  // 25 = A/B: the fp32-MFMA tight-K kernel
+  if (!(g.kd == 5 && g.kh == 5 && g.kw == 5 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 2 && g.ph == 2 && g.pw == 2)) return false;
+  if (!(g.SD == g.DD && g.SH == g.DH && g.SW == g.DW)) return false;
+  if (g.CK < 1 || g.CK > 4 || g.CN != 32 || g.bias || g.prelu) return false;
+  if (g.DW < 12 || g.DH < 8 || g.DD < 4) return false;
+  if (g.dld % 4 || (((uintptr_t)g.dst) & 15)) return false;
+  if (join) {  // the fused join backward: a plain (not accumulating) store of float4 granules, option "tk_join"
+    if (!ctx->tk_join || g.accumulate) return false;
+    if (join->xld % 4 || join->bld % 4 || (((uintptr_t)join->x) & 15) || (((uintptr_t)join->b) & 15)) return false;
+    if (join->db && (join->dbld % 4 || (((uintptr_t)join->db) & 15))) return false;
+    if (!(join->scale && join->shift && join->alpha_in && join->alpha && join->mean && join->invstd && join->maxes)) return false;
+  }
+  return true;
+}
+
+int msk_gconv_tk_h2(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int B, int swap, TKJoin* join) {
+  if (!msk_gconv_tk_h2_accepts(ctx, g, join)) return 0;
   unsigned short* wb = (unsigned short*)msk_workspace2(ctx, (size_t)kTKSteps * 2 * 2 * 64 * 8 * sizeof(unsigned short));
   if (!wb) return -1;
   const float* x_amax = g.in_amax ? g.in_amax : msk_absmax(ctx, g.src, g.sld, g.CK, (long)g.N * g.SD * g.SH * g.SW);
@@ -410,14 +553,25 @@ int msk_gconv_tk_h2(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, i
   if (nblk > 0x7fffffff) return 0;
   a.nblk = (int)nblk;
   a.x_amax = x_amax; a.w_amax = w_amax;
-  const char* tag = "conv_tk_h2";
+  if (join) {
+    float* partial = (float*)msk_workspace(ctx, (size_t)nblk * 4 * 32 * sizeof(float));
+    if (!partial) return -1;
+    a.jx = join->x; a.jxld = join->xld; a.jb = join->b; a.jbld = join->bld; a.jdb = join->db; a.jdbld = join->dbld;
+    a.jcoef[0] = join->scale; a.jcoef[1] = join->shift; a.jcoef[2] = join->alpha_in;
+    a.jcoef[3] = join->alpha; a.jcoef[4] = join->mean; a.jcoef[5] = join->invstd;
+    a.partial = partial; a.maxes = (unsigned*)join->maxes;
+    join->partial = partial; join->nb = a.nblk;
+  }
+  // both forms keep the "conv_tk_h2" prefix: the full-size parity test looks for this kernel at 128^3 under it
+  const char* tag = join ? "conv_tk_h2_join" : "conv_tk_h2";
   if (ctx->prof && ctx->prof_shapes) {
     char buf[160];
-    snprintf(buf, sizeof(buf), "conv_tk_h2[ck=%d,cn=%d,n=%d,dhw=%dx%dx%d,acc=%d]", g.CK, g.CN, g.N, g.DD, g.DH, g.DW, g.accumulate);
+    snprintf(buf, sizeof(buf), "%s[ck=%d,cn=%d,n=%d,dhw=%dx%dx%d,acc=%d]", tag, g.CK, g.CN, g.N, g.DD, g.DH, g.DW, g.accumulate);
     tag = msk_intern_tag(ctx, buf);
   }
   msk_launch_scope ls(ctx, tag);
-  hipLaunchKernelGGL(conv_tk_h2_k, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a);
+  if (join) hipLaunchKernelGGL(conv_tk_h2_k<true>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(conv_tk_h2_k<false>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a);
   MSK_LAUNCH_CHECK(ctx);
   return 1;
 }

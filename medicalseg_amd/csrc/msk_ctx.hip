@@ -615,6 +615,10 @@ int msk_set_option(msk_ctx* ctx, const char* key, int value) {
     ctx->bwd_fuse = value < 0 ? -1 : (value > 2 ? 2 : value);
     return 0;
   }
+  if (strcmp(key, "tk_join") == 0) {  // 0 = msk_conv3d_bwd_bnact_join declines: the join backward keeps its own pass (A/B)
+    ctx->tk_join = value != 0;
+    return 0;
+  }
   if (strcmp(key, "foldn_wgs") == 0) {
     ctx->foldn_wgs = value > 0 ? value : 0;
     return 0;

@@ -325,20 +325,7 @@ __device__ __forceinline__ void split_vc(long i, int cv, int cshift, long& v, in
   }
 }
 
-// max of a block folded into an amax array (msk_wbf.h: kWbfAmaxWays floats, bits of non-negative floats): ONE atomic per
-// block, on the way blockIdx % ways, nothing waits for it (per-wavefront atomics on a single address cost 0.2 ms per step)
-__device__ __forceinline__ void block_atomic_max(unsigned* amax, float m) {
-  __shared__ float shm_amax[kThreads / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  __syncthreads();  // a second call reuses the array
-  if ((threadIdx.x & 63) == 0) shm_amax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, shm_amax[i]);
-    if (m > 0.f) (void)atomicMax(amax + (blockIdx.x + blockIdx.y * 7u) % kWbfAmaxWays, __float_as_uint(m));
-  }
-}
+// (block_atomic_max: msk_wbf.h)
 
 template <int V>
 __global__ void __launch_bounds__(kThreads)
@@ -1281,6 +1268,16 @@ inline void noop_launches(msk_ctx* ctx) {
 int msk_bn_stats_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* stats, const msk_bn_fin* fin) {
   msk_launch_scope ls(ctx, "bn_stats_merge");
   hipLaunchKernelGGL(bn_stats_merge, dim3(C), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, C, C, stats, fin ? *fin : msk_bn_fin{});
+  MSK_LAUNCH_CHECK(ctx);
+  noop_launches(ctx);
+  return 0;
+}
+
+int msk_join_sums_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* unit_sums, float* u_dbeta, float* u_dgamma,
+                        float* u_dalpha, float* dalpha) {
+  msk_launch_scope ls(ctx, "sums_merge");
+  hipLaunchKernelGGL(sums_merge_k, dim3(4 * C), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, C, 4 * pow2ceil(C / 4), 4, unit_sums, 0,
+                     u_dbeta, u_dgamma, u_dalpha, dalpha);
   MSK_LAUNCH_CHECK(ctx);
   noop_launches(ctx);
   return 0;

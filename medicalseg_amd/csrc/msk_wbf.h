@@ -87,6 +87,20 @@ __device__ __forceinline__ float wbf_scale_of(const float* amax) {
   if (!amax) return 1.f;
   return wbf_scale_from(wbf_amax_of(amax));
 }
+// max of a block (<= 256 threads) folded into an amax array (bits of non-negative floats): ONE atomic per block, on the way
+// blockIdx % ways, nothing waits for it (per-wavefront atomics on a single address cost 0.2 ms per step)
+__device__ __forceinline__ void block_atomic_max(unsigned* amax, float m) {
+  __shared__ float shm_amax[256 / 64];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  __syncthreads();  // a second call reuses the array
+  if ((threadIdx.x & 63) == 0) shm_amax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, shm_amax[i]);
+    if (m > 0.f) (void)atomicMax(amax + (blockIdx.x + blockIdx.y * 7u) % kWbfAmaxWays, __float_as_uint(m));
+  }
+}
 
 // Stage 1 (wbf_tin_k<MODE>): MODE 0  V = B^T x  (8 transformed values per 4 inputs, sliding 8-wide window along w)
 //                            MODE 1  Y = A dy   (8 values per 4 output gradients: the adjoint of the output transform)

@@ -210,6 +210,12 @@ class UpTransition(nn.Layer):
         out, unit = _run_ops(self.ops, xcat, xcat)
         return self._join.forward(out, xcat, unit=unit)
 
+    def join_for_consumer(self):
+        """(join, share_b) as backward() will run it: for the block behind this one, whose first data gradient may take the
+        join's backward along (nn.AddAct.backward_in_dgrad)"""
+        ops = list(self.ops)
+        return self._join, bool(ops) and ops[0]._unit.x is self._xcat
+
     def backward(self, dout):
         xcat, half = self._xcat, self.outChans // 2
         ops = list(self.ops)
@@ -269,9 +275,10 @@ class OutputTransition(nn.Layer):
         self._o = o
         return self.conv2.run_forward(o)
 
-    def backward(self, dlogits):
+    def backward(self, dlogits, join=None):
+        """join: see nn.ConvBNAct.backward"""
         self.conv2.run_backward(self._o, dlogits, need_dx=True)
-        self._unit.backward(self._o.grad)
+        self._unit.backward(self._o.grad, join=join)
 
 
 @manager.MODELS.add_component
@@ -388,8 +395,12 @@ class VNet(nn.Layer):
             # the dense twin of out16 (forward) is what down_tr32 read: its data gradient accumulates into out16's gradient
             if twin is not None and out16.grad is not None:
                 twin.grad, twin.grad_written = out16.grad, True
-        for block, dout in ((self.out_tr, lambda: dlogits),
-                            (self.up_tr32, lambda: self._feat.grad),
+        # out_tr.conv1's data gradient is the output gradient of up_tr32's join and of nothing else: that join's backward runs in
+        # the kernel's epilogue where it can (the 32-channel gradient at full resolution is then never written)
+        self.out_tr.backward(dlogits, join=self.up_tr32.join_for_consumer())
+        self._grads_ready(self.out_tr)
+        for block, dout in (
+                            (self.up_tr32, lambda: self._feat.grad),      # (None when the join was taken along)
                             (self.up_tr64, lambda: self.up_tr32._x.grad),
                             (self.up_tr128, lambda: self.up_tr64._x.grad),
                             (self.up_tr256, lambda: self.up_tr128._x.grad),

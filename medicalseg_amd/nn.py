@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -652,8 +653,10 @@ class ConvBNAct:
         self.out = out
         return out
 
-    def backward(self, dout: Tensor, need_dx=True, res_needs_grad=True):
-        """dout: gradient w.r.t. the unit's output (may be a channel slice)."""
+    def backward(self, dout: Tensor, need_dx=True, res_needs_grad=True, join=None):
+        """dout: gradient w.r.t. the unit's output (may be a channel slice).  join: (AddAct, share_b) -- the residual join that
+        produced this unit's input and whose backward runs next with that share_b: its backward may be taken along by this unit's
+        data-gradient kernel (AddAct.backward_in_dgrad; the join's own backward call is then a no-op)."""
         if self.bn_mode == 3:
             raise RuntimeError("backward through a forward pass run under nn.fused_inference() (BN folded into the "
                                "convolution: no pre-activation tensor was kept)")
@@ -787,6 +790,11 @@ class ConvBNAct:
                 x.grad_written = True
                 self.dy = dy
                 return
+        if (join is not None and res is None and need_dx and type(self.conv) is Conv3D and self.bn_mode == 1
+                and not isinstance(self.act, ELU) and self.conv.s == (1, 1, 1)
+                and join[0].backward_in_dgrad(self, join[1], dout, dy, sums_total, m_total)):
+            self.dy = dy
+            return
         dres = NULL_TENSOR
         dres_acc = 0
         if res is not None and res_needs_grad and res.c == y.c:
@@ -820,6 +828,7 @@ class AddAct:
         this join, on the convolution output (one pass instead of two, `a` is never written).  out: destination (may be a
         channel slice of a wider buffer: zero-copy skip connections, UpTransition.reserve_concat)."""
         self.a, self.b = a, b
+        self._bwd_done = False
         self.unit = unit if (unit is not None and getattr(unit, "deferred", False)) else None
         if out is None:
             out = a.empty_like()
@@ -836,13 +845,68 @@ class AddAct:
         else:
             a.dev.call("msk_affine_act_fwd_amax", a.msk(), None, None, b.msk(), _fp(self.act._weight.ptr), out.msk(),
                        _amax_for(out))
+        self.out = out
         return out
+
+    def backward_in_dgrad(self, consumer: "ConvBNAct", share_b, dout: Tensor, dy: Tensor, sums_total, m_total) -> bool:
+        """This join's backward inside the data-gradient kernel of `consumer`, the conv -> BN -> PReLU unit that reads the join's
+        output (out_tr.conv1 behind up_tr32, vnet.py:154,173): msk_conv3d_bwd_bnact_join runs the rest of the consumer's backward
+        (dy, its weight gradient) and leaves what backward(share_b=True) leaves -- the join's output gradient is neither
+        allocated nor written.  False: not eligible, nothing launched, nothing changed."""
+        dev = dout.dev
+        a, b, u = self.a, self.b, getattr(self, "unit", None)
+        x, conv = consumer.x, consumer.conv
+        if getattr(dev.lib.msk_conv3d_bwd_bnact_join, "missing", False):
+            # a library built before this entry point (or the no-compute stand-in of the host tests): the separate calls, said once
+            warnings.warn(f"{_lib.LIB_PATH} does not export msk_conv3d_bwd_bnact_join: the residual join behind the output block "
+                          "runs as separate kernels; rebuild with ./build.sh", RuntimeWarning)
+            return False
+        if (u is None or not FUSE_SMALL or isinstance(self.act, ELU)
+                or getattr(self, "out", None) is not x or x.grad is not None or getattr(x, "grad_from", None) is not None
+                or a.grad_written or b.grad_written or a.c % 4):
+            return False
+        ga, gb = a.ensure_grad(), b.ensure_grad()     # (as backward() does: kept when the call below declines)
+        share_b = bool(share_b and SHARE_JOIN_GRAD and ga.ld == gb.ld)    # as backward() decides it
+        if not all(t.ld % 4 == 0 and t.ptr % 16 == 0 for t in (a, b, ga, gb, u.y)):
+            return False
+        sc, usc = consumer.bn.scratch(dev), u.bn.scratch(dev)
+        y = consumer.y
+        xf = getattr(conv, "_xform", None)
+        xfp = xf[0] if (xf is not None and xf[1] == x.ptr and xf[2] == dev.arena.gen) else None
+        dya = _amax_for(dy)
+        xa = x.amax if (x.amax and PRODUCER_AMAX and xfp is None) else None
+        mx = dev.amax_new(2)
+        rc = dev.lib.msk_conv3d_bwd_bnact_join(
+            dev.ctx, conv.desc(), x.msk(), _fp(conv.weight.ptr), y.msk(), _fp(sc["scale"]), _fp(sc["shift"]),
+            _fp(_act_alpha(consumer.act)), _fp(sc["mean"]), _fp(sc["invstd"]), _fp(consumer.bn.weight.ptr), dout.msk(),
+            _fp(sums_total), C.c_double(m_total), dy.msk(), dya, _fp(conv.weight.grad_ptr), 1, _fp(xfp), _fp(xa),
+            u.y.msk(), _fp(usc["scale"]), _fp(usc["shift"]), _fp(u.act._weight.ptr), b.msk(), _fp(self.act._weight.ptr),
+            _fp(usc["mean"]), _fp(usc["invstd"]), ga.msk(), 0, NULL_TENSOR if share_b else gb.msk(), 0,
+            _fp(self.act._weight.grad_ptr), _fp(usc["sums"]), _fp(mx), 0,
+            _fp(u.bn.weight.grad_ptr), _fp(u.bn.bias.grad_ptr), _fp(u.act._weight.grad_ptr))
+        if rc < 0:
+            raise MskError(f"msk_conv3d_bwd_bnact_join failed: {_lib.last_error(dev.ctx)}")
+        if rc != 0:
+            return False
+        _count_flops(conv, x.n, dy.d * dy.h * dy.w, 2)
+        conv._xform = None
+        u.presummed, u.presummed_pg, u.presummed_maxes = True, True, mx
+        a.grad_written = True
+        if share_b:
+            b.grad_from = ga      # b.grad itself is still unwritten
+        else:
+            b.grad_written = True
+        self._bwd_done = True
+        return True
 
     def backward(self, dout: Tensor, share_b=False):
         """share_b: d(a + b) goes to both operands unchanged -- write it ONCE (a.grad) and mark b's gradient as living there
         (b.grad_from) when nothing has been written to b.grad yet; the layer that accumulates onto it next reads a.grad as its old
         values (ConvBNAct.backward -> msk_conv3d_bwd_bnact_acc).  The caller guarantees that this layer is b's next consumer and
         calls nn.materialize_grad(b) afterwards in case it was not."""
+        if getattr(self, "_bwd_done", False):     # taken along by the consumer's data gradient (backward_in_dgrad): dout was never written
+            self._bwd_done = False
+            return
         dev = dout.dev
         a, b = self.a, self.b
         Cn = a.c
