@@ -449,6 +449,26 @@ int msk_tta_accumulate(msk_ctx* ctx, msk_tensor logits, int mask, msk_tensor acc
  * nothing data-dependent can fail; shape mismatch, mask outside 0..7 and passes < 1 are argument errors.             */
 int msk_tta_finish(msk_ctx* ctx, msk_tensor acc, int passes, msk_tensor probs, int32_t* pred);
 
+/* ---- sliding-window inference (core/infer.py sliding_window_inference) ------ */
+/* Crop patches.n windows of patches' extent out of vol [N,D,H,W,Cin] with implicit padding.  origins: HOST array of
+ * patches.n x 4 int32 (n, d0, h0, w0), the window's first voxel in VOLUME coordinates (may be negative, the window may run
+ * past the end):  patches[b][z][y][x][:] = vol[n][d0+z][h0+y][w0+x][:] where that voxel exists, cval where it does not.  */
+int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_t* origins, float cval);
+/* Add logits.n windows of logits [B,rd,rh,rw,C], weighted per voxel, into acc [N,D,H,W,C].  td / th / tw: DEVICE tables of
+ * nd x rd, nh x rh, nw x rw floats (one row per window start of that axis; core/infer.py SlidingPlan normalises them per axis,
+ * so the weights of all windows over a voxel sum to 1 and no division follows).  origins: HOST array of logits.n x 7 int32
+ * (n, d0, h0, w0, id, ih, iw): origin as above and the table row of each axis.  For the windows in order, for every window
+ * voxel inside the volume (the padding is skipped) and every channel, in fp32 with one rounding per operation, never an FMA:
+ *     w   = (td[id][z] * th[ih][y]) * tw[iw][x]
+ *     acc = acc + (w * logit)
+ * Both entry points: asynchronous on the context stream (origins is read before the call returns), no atomics, one launch
+ * per window so that overlapping windows of one call are added in order; any ld >= c on every tensor (16 bytes per lane
+ * where the tensors are dense and row start and row length are whole quads, 4 bytes per lane otherwise); nothing
+ * data-dependent can fail.  Argument errors, reported before any launch: a channel mismatch, n outside the batch, a table
+ * row outside its table, a window that does not intersect the volume, patches overlapping vol, acc overlapping logits.   */
+int msk_sw_accumulate(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, const float* td, int nd, const float* th, int nh,
+                      const float* tw, int nw, msk_tensor acc);
+
 /* ---- loss ------------------------------------------------------------------ */
 /* losses/loss_utils.py:31-40 class_weights: w_c = sum(1-softmax_c)/sum(softmax_c) */
 int msk_class_weights(msk_ctx* ctx, msk_tensor logits, float* weights);

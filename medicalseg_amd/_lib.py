@@ -132,6 +132,8 @@ SIGNATURES = {
     "msk_flip_axes": (_i, [_vp, _T, _T, _i]),
     "msk_tta_accumulate": (_i, [_vp, _T, _i, _T, _i]),
     "msk_tta_finish": (_i, [_vp, _T, _i, _T, _vp]),
+    "msk_sw_gather": (_i, [_vp, _T, _T, _vp, _f]),
+    "msk_sw_accumulate": (_i, [_vp, _T, _vp, _vp, _i, _vp, _i, _vp, _i, _T]),
     "msk_class_weights": (_i, [_vp, _T, _vp]),
     "msk_loss_fwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _vp]),
     "msk_loss_bwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _f, _f, _T]),

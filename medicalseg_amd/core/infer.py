@@ -1,6 +1,7 @@
 """Inference helpers (reference medicalseg/core/infer.py:62-94): forward + argmax."""
 import collections.abc
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -169,3 +170,207 @@ def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_a
         dev.call("msk_tta_finish", acc.msk(), len(passes), probs.msk(), C.c_void_p(ptr))
     pred = IntTensor(dev, ptr, (probs.n, 1, probs.d, probs.h, probs.w), dev.arena.gen)
     return (pred, probs, plain) if with_plain else (pred, probs)
+
+
+# ----------------------------------------------------------------------------------------
+# sliding-window inference: the net on overlapping roi_size windows at native resolution, blended with a window weight that
+# falls off towards the window border (the reference has it in its nnunet subtree only, not in the VNet path)
+# ----------------------------------------------------------------------------------------
+class SlidingPlan:
+    """Everything of a sliding-window prediction that depends only on geometry: one volume extent (D, H, W), one roi_size
+    (rd, rh, rw).  Per axis, with `size` the volume extent and `r` the window extent:
+
+      padded extent   P = max(size, r); a volume smaller than the window is padded with before = (r - size) // 2 voxels in
+                      front and the rest behind.  The padding is implicit (msk_sw_gather fills it, msk_sw_accumulate skips it).
+      window starts   in padded coordinates: [0] if P == r, else interval = max(1, int(r * (1 - overlap))),
+                      num = ceil((P - r) / interval) + 1, start_i = min(i * interval, P - r).
+      profile         g[k], float64: 1 ('constant') or exp(-0.5 * ((k - (r - 1) / 2) / (sigma_scale * r)) ** 2) ('gaussian').
+      coverage        S[p] = sum over the windows that contain p of g[p - start_i], float64, in window order.
+      table           T[i][k] = float32(g[k] / S[start_i + k]), one row per window start.
+
+    The windows are the full product of the three start lists and the 3-D weight is the product of the three profiles, so
+    the 3-D coverage is the product of the three S: normalising per axis normalises the blend, and no weight-sum volume, no
+    division and no finish pass exist anywhere.
+
+    Attributes: shape, roi_size, overlap, mode, sigma_scale, padded, before, starts (three lists), tables (three float32
+    arrays [len(starts[a]), roi_size[a]]).  ValueError: overlap outside [0, 1), a non-positive roi_size or shape, an unknown
+    mode, a coverage of zero or a table entry that is zero, subnormal or not finite (a sigma_scale so small that the profile
+    underflows)."""
+
+    def __init__(self, shape, roi_size, overlap=0.5, mode='gaussian', sigma_scale=0.125):
+        shape, roi_size = tuple(shape), tuple(roi_size)
+        if len(shape) != 3 or len(roi_size) != 3:
+            raise ValueError("SlidingPlan: shape and roi_size are (D, H, W) triples, got %r and %r" % (shape, roi_size))
+        for v in shape + roi_size:
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 1:
+                raise ValueError("SlidingPlan: shape and roi_size must be positive integers, got %r and %r" % (shape, roi_size))
+        overlap = float(overlap)
+        if not 0.0 <= overlap < 1.0:
+            raise ValueError("SlidingPlan: overlap must satisfy 0 <= overlap < 1, got %r" % (overlap,))
+        if mode not in ('constant', 'gaussian'):
+            raise ValueError("SlidingPlan: mode is 'constant' or 'gaussian', got %r" % (mode,))
+        if mode == 'gaussian' and not float(sigma_scale) > 0.0:
+            raise ValueError("SlidingPlan: sigma_scale must be positive, got %r" % (sigma_scale,))
+        self.shape = tuple(int(v) for v in shape)
+        self.roi_size = tuple(int(v) for v in roi_size)
+        self.overlap, self.mode, self.sigma_scale = overlap, mode, float(sigma_scale)
+        self.padded, self.before, self.starts, self.tables = [], [], [], []
+        tiny = np.finfo(np.float32).tiny
+        for size, r in zip(self.shape, self.roi_size):
+            P = max(size, r)
+            if P == r:
+                starts = [0]
+            else:
+                interval = max(1, int(r * (1 - overlap)))
+                num = -(-(P - r) // interval) + 1
+                starts = [min(i * interval, P - r) for i in range(num)]
+            with np.errstate(all='ignore'):
+                if mode == 'constant':
+                    g = np.ones(r, np.float64)
+                else:
+                    # math.exp, the C library's: numpy's vector exp may differ from it in the last bit
+                    g = np.array([math.exp(-0.5 * ((k - (r - 1) / 2) / (self.sigma_scale * r)) ** 2) for k in range(r)])
+                S = np.zeros(P, np.float64)
+                for s in starts:
+                    S[s:s + r] += g
+                if not (S != 0).all():
+                    raise ValueError("SlidingPlan: a voxel has zero window weight (sigma_scale = %r underflows at extent %d)"
+                                     % (sigma_scale, r))
+                T = np.stack([(g / S[s:s + r]).astype(np.float32) for s in starts])
+            if not (np.isfinite(T).all() and (T >= tiny).all()):
+                raise ValueError("SlidingPlan: a window weight is zero, subnormal or not finite (sigma_scale = %r at extent %d)"
+                                 % (sigma_scale, r))
+            self.padded.append(P)
+            self.before.append((r - size) // 2 if size < r else 0)
+            self.starts.append(starts)
+            self.tables.append(T)
+        self.padded, self.before = tuple(self.padded), tuple(self.before)
+
+    @property
+    def key(self):
+        return (self.shape, self.roi_size, self.overlap, self.mode, self.sigma_scale)
+
+    def windows(self, n=1):
+        """The windows of a batch of n volumes in order: batch item slowest, then the d, h and w starts, w fastest; each is
+        (n, id, ih, iw), indices into the three start lists."""
+        nd, nh, nw = (len(s) for s in self.starts)
+        return [(b, i, j, k) for b in range(int(n)) for i in range(nd) for j in range(nh) for k in range(nw)]
+
+    def origin(self, window):
+        """(n, d0, h0, w0): the window's first voxel in VOLUME coordinates, start - before per axis; may be negative, and the
+        window may run past the end of the volume"""
+        b, i, j, k = window
+        return (b, self.starts[0][i] - self.before[0], self.starts[1][j] - self.before[1], self.starts[2][k] - self.before[2])
+
+
+def _sw_cache(dev):
+    return dev.__dict__.setdefault("_sw_buffers", {})
+
+
+def _sw_buffer(dev, role, n, d, h, w, c):
+    """The persistent device tensor of a role (the patch batch, the accumulator, the kept input) outside the activation arena:
+    they have to outlive the forwards.  One per role: a call at the same shape reuses it and allocates nothing, a call at
+    another shape frees it first -- native-resolution volumes differ in extent, and a whole-volume accumulator per distinct
+    extent (0.9 GB at 300 x 512 x 512, C = 3) would otherwise stay for the device's lifetime.  sliding_release frees them."""
+    cache = _sw_cache(dev)
+    shape = (int(n), int(d), int(h), int(w), int(c))
+    t = cache.get((role,))
+    if t is not None and (t.n, t.d, t.h, t.w, t.c) != shape:
+        dev.free(cache.pop((role,)).ptr)
+        t = None
+    if t is None:
+        t = cache[(role,)] = Tensor.empty(dev, *shape, arena=False)
+    return t
+
+
+def _sw_plan(dev, shape, roi_size, overlap, mode, sigma_scale):
+    """-> (SlidingPlan, [td, th, tw] device pointers): the plan of a geometry and its three tables, uploaded once"""
+    cache = _sw_cache(dev)
+    key = ("plan", tuple(int(v) for v in shape), tuple(roi_size), float(overlap), mode, float(sigma_scale))
+    hit = cache.get(key)
+    if hit is None:
+        plan = SlidingPlan(shape, roi_size, overlap, mode, sigma_scale)
+        ptrs = []
+        for T in plan.tables:
+            p = dev.malloc(T.nbytes)
+            dev.h2d(p, T)
+            ptrs.append(p)
+        hit = cache[key] = (plan, ptrs)
+    return hit
+
+
+def sliding_release(dev):
+    """Free the persistent buffers and plan tables of sliding_window_inference on `dev`.  The buffers are one per role (see
+    _sw_buffer); the plans with their three small device tables are kept per geometry, for the device's lifetime otherwise.
+    The `logits` an earlier call returned IS the accumulator freed here: it must not be used after a release (its liveness
+    check cannot know; until the next forward it still passes)."""
+    for key, v in dev.__dict__.pop("_sw_buffers", {}).items():
+        if key[0] == "plan":
+            for p in v[1]:
+                dev.free(p)
+        else:
+            dev.free(v.ptr)
+
+
+def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', sigma_scale=0.125, sw_batch_size=1, cval=0.0,
+                             ori_shape=None, transforms=None):
+    """Window-by-window prediction at native resolution: the net runs on the overlapping `roi_size` windows of SlidingPlan
+    (`overlap`, implicit padding with `cval` where the volume is smaller than the window), sw_batch_size windows per forward
+    (the last batch may be smaller), and the outputs are blended on the device with the plan's normalised window weights
+    (mode 'gaussian' or 'constant'): msk_sw_gather -> model(patches)[0] -> msk_sw_accumulate per batch, in window order.
+
+    Returns (pred IntTensor [N,1,D,H,W], logits Tensor [N,C,D,H,W]), the pair inference() returns, so a caller can swap one
+    for the other.  What is blended are the LOGITS (the network's output), not probabilities: evaluate's loss and mdice need
+    whole-volume logits, and the softmax / AUC / argmax downstream then work unchanged.  `logits` is the persistent
+    accumulator itself, stamped with the arena generation of the last forward: no copy, valid until the next forward, as
+    inference()'s are.  With `ori_shape` different from `im`'s extent and Resize3D ops in `transforms`, the blended logits are
+    resized back (reverse_transform) and the argmax is taken after that, as inference() does.
+
+    Runs in one nn.fused_inference scope.  The plan with its device tables, the patch batch, the accumulator and (if `im`
+    lives in the activation arena, which every forward resets) a copy of `im` are persistent buffers: a second call at the
+    same shapes allocates no device memory, a call at other shapes frees and replaces the buffers whose shape changed (so
+    `logits` of an earlier call is gone then, as it is after the next forward); sliding_release frees them."""
+    if not isinstance(sw_batch_size, (int, np.integer)) or isinstance(sw_batch_size, bool) or sw_batch_size < 1:
+        raise ValueError("sliding_window_inference: sw_batch_size must be a positive integer, got %r" % (sw_batch_size,))
+    if not isinstance(im, Tensor):
+        im = to_tensor(im)
+    dev = im.dev
+    plan, (td, th, tw) = _sw_plan(dev, (im.d, im.h, im.w), roi_size, overlap, mode, sigma_scale)
+    rd, rh, rw = plan.roi_size
+    if im.gen is not None:          # an activation: the first forward would reset the arena under it
+        kept = _sw_buffer(dev, "im", im.n, im.d, im.h, im.w, im.c)
+        dev.call("msk_flip_axes", im.msk(), kept.msk(), 0)
+        im = kept
+    windows = plan.windows(im.n)
+    batch = min(int(sw_batch_size), len(windows))
+    patches = _sw_buffer(dev, "patches", batch, rd, rh, rw, im.c)
+    rows = [C.c_int(len(s)) for s in plan.starts]
+    acc = None
+    with nn.fused_inference():
+        for k in range(0, len(windows), batch):
+            group = windows[k:k + batch]
+            origins = np.array([plan.origin(wd) + wd[1:] for wd in group], np.int32)
+            corners = np.ascontiguousarray(origins[:, :4])
+            x = patches if len(group) == batch else Tensor(dev, patches.ptr, len(group), rd, rh, rw, im.c)
+            dev.call("msk_sw_gather", im.msk(), x.msk(), corners.ctypes.data_as(C.c_void_p), C.c_float(cval))
+            logits = model(x)
+            if not isinstance(logits, collections.abc.Sequence):
+                raise TypeError("The type of logits must be one of collections.abc.Sequence, e.g. list, tuple. "
+                                "But received {}".format(type(logits)))
+            logit = logits[0]
+            if (logit.n, logit.d, logit.h, logit.w) != (len(group), rd, rh, rw):
+                raise ValueError("sliding_window_inference: the model maps a window batch of extent %r to %r; the logits "
+                                 "must keep the window's extent" % ((len(group), rd, rh, rw), (logit.n, logit.d, logit.h, logit.w)))
+            if acc is None:
+                acc = _sw_buffer(dev, "acc", im.n, im.d, im.h, im.w, logit.c)
+                dev.memset(acc.ptr, 0, acc.voxels * acc.c * 4)
+            dev.call("msk_sw_accumulate", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
+                     C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], acc.msk())
+    # stamped like an activation of the last forward: stale after the next one, a new object per call
+    logit = Tensor(dev, acc.ptr, acc.n, acc.d, acc.h, acc.w, acc.c, acc.c, dev.arena.gen)
+    if ori_shape is not None and tuple(ori_shape) != tuple(logit.shape[2:]):
+        logit = reverse_transform(logit, ori_shape, transforms, mode='bilinear')
+    ptr = dev.arena.alloc(logit.voxels * 4)
+    dev.call("msk_argmax_c", logit.msk(), C.c_void_p(ptr))
+    pred = IntTensor(dev, ptr, (logit.n, 1, logit.d, logit.h, logit.w), dev.arena.gen)
+    return pred, logit

@@ -46,8 +46,17 @@ def _image_info(dataset_json, idx):
 
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
              save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False, surface_metrics=False,
-             surface_spacing=None, aug_eval=False, scales=1.0, flip_axes=()):
-    """aug_eval: the hard-label prediction (what pred_transform, hard_metrics, surface_metrics and the saved arrays see) and
+             surface_spacing=None, aug_eval=False, scales=1.0, flip_axes=(), sliding_window=None, sw_overlap=0.5,
+             sw_mode='gaussian', sw_batch_size=1):
+    """sliding_window: a roi (rd, rh, rw); the logits and the prediction of every volume come from
+    ``infer.sliding_window_inference(roi_size=sliding_window, overlap=sw_overlap, mode=sw_mode, sw_batch_size=sw_batch_size)``
+    -- the net on overlapping windows at the volume's own resolution, blended on the device -- in place of the one forward of
+    ``infer.inference``; everything downstream (loss, mdice, hard and surface metrics, AUC, saved arrays) is unchanged.
+    Together with aug_eval it raises ValueError: combining the two is out of scope here.  The call keeps its device buffers
+    (one accumulator, patch batch and plan tables per geometry; volumes of another extent replace the accumulator) after the
+    loop for the next evaluation; ``infer.sliding_release(device)`` frees them.
+
+    aug_eval: the hard-label prediction (what pred_transform, hard_metrics, surface_metrics and the saved arrays see) and
     the AUC scores come from ``infer.aug_inference(scales=scales, flip_axes=flip_axes)``: the mean softmax over the mirrored
     (flip_axes: 0/1/2 = D/H/W, every subset) and rescaled passes and its argmax, in place of the single pass's.  ``mdice``
     and the loss stay those of the plain pass (its logits come back from the same call), so ``scales`` must contain 1.0.
@@ -75,6 +84,8 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     if aug_eval and (1.0, 0) not in infer.tta_passes(scales, flip_axes):
         raise ValueError("evaluate(aug_eval=True): scales must contain 1.0 (mdice and the loss are the plain pass's), got %r"
                          % (scales,))
+    if sliding_window is not None and aug_eval:
+        raise ValueError("evaluate: sliding_window together with aug_eval=True is not supported")
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -109,6 +120,11 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                 if tuple(label.shape[-3:]) != tuple(logits.shape[2:]):      # as inference() does before the loss
                     logits = infer.reverse_transform(logits, label.shape[-3:], eval_dataset.transforms.transforms,
                                                      mode='bilinear')
+            elif sliding_window is not None:
+                pred, logits = infer.sliding_window_inference(model, to_tensor(im), sliding_window, overlap=sw_overlap,
+                                                              mode=sw_mode, sw_batch_size=sw_batch_size,
+                                                              ori_shape=label.shape[-3:],
+                                                              transforms=eval_dataset.transforms.transforms)
             else:
                 pred, logits = infer.inference(model, to_tensor(im), ori_shape=label.shape[-3:],
                                                transforms=eval_dataset.transforms.transforms)

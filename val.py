@@ -27,6 +27,14 @@ def parse_args(argv=None):
                    help='With --aug_eval: scales of the passes; must contain 1.0')
     p.add_argument('--flip_axes', dest='flip_axes', nargs='*', type=int, default=(),
                    help='With --aug_eval: axes to mirror, 0 1 2 = D H W; every subset is one pass')
+    p.add_argument('--sliding_window', dest='sliding_window', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'),
+                   help='Predict window by window at native resolution with this roi and blend the logits')
+    p.add_argument('--sw_overlap', dest='sw_overlap', type=float, default=0.5,
+                   help='With --sliding_window: overlap of neighbouring windows, 0 <= overlap < 1')
+    p.add_argument('--sw_mode', dest='sw_mode', type=str, default='gaussian', choices=('gaussian', 'constant'),
+                   help='With --sliding_window: window weight')
+    p.add_argument('--sw_batch_size', dest='sw_batch_size', type=int, default=1,
+                   help='With --sliding_window: windows per forward')
     return p.parse_args(argv)
 
 
@@ -47,7 +55,8 @@ def main(args):
     print(evaluate(model, val_dataset, cfg.loss, num_workers=args.num_workers, print_detail=args.print_detail,
                    auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device,
                    surface_metrics=args.surface_metrics, aug_eval=args.aug_eval, scales=args.scales,
-                   flip_axes=args.flip_axes))
+                   flip_axes=args.flip_axes, sliding_window=args.sliding_window, sw_overlap=args.sw_overlap,
+                   sw_mode=args.sw_mode, sw_batch_size=args.sw_batch_size))
 
 
 if __name__ == '__main__':
