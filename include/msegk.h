@@ -469,6 +469,36 @@ int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_
 int msk_sw_accumulate(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, const float* td, int nd, const float* th, int nh,
                       const float* tw, int nw, msk_tensor acc);
 
+/* ---- random patch cropping (transforms.RandomPatchCrop3D) -------------------- */
+/* Bytes of workspace msk_patch_select needs for a label volume of `voxels` voxels (in [1, 2^31)) and num_classes in
+ * [1, 256]: the class totals and one row of num_classes 32-bit counters per 4096 voxels.  Needs no context and no GPU.  */
+int msk_patch_workspace(long voxels, int num_classes, size_t* bytes);
+/* Choose n_patches (1..16) patch origins of extent rd x rh x rw in a DEVICE label volume [d,h,w] int32, as
+ * tests/patch_reference.py states it.  counts[c] = voxels with label c, 0 <= c < num_classes (other values, 255 or negative,
+ * are not counted); present = the classes of `classes` (HOST, n_classes in 0..32 strictly ascending values inside
+ * [0, num_classes)) with counts > 0, m of them.  words: HOST array of n_patches x 6 uint32 (force_fg, w_cls, w_rank, w_d, w_h,
+ * w_w); every product below is an exact unsigned 64-bit one.  With force_fg != 0 and m > 0: cls = present[(w_cls * m) >> 32],
+ * r = (w_rank * counts[cls]) >> 32, the centre is the r-th voxel of class cls in raster order, and per axis
+ * origin = -((roi - dim) / 2) if dim <= roi, else min(max(centre - roi / 2, 0), dim - roi).  Otherwise cls = -1,
+ * centre = (-1,-1,-1) and per axis origin = -((roi - dim) / 2) if dim <= roi, else (w_axis * (dim - roi + 1)) >> 32.
+ * sel (DEVICE): n_patches records of 8 int32: d0, h0, w0, cls, cz, cy, cx, 0.  counts (DEVICE, num_classes int32) may be
+ * null.  workspace (DEVICE): msk_patch_workspace bytes, 4-byte aligned; its contents mean nothing to the caller.  The label is
+ * read once (16 bytes per lane where it is 16-byte aligned), plus one 16 KiB chunk of it per foreground patch; a call in which
+ * no patch has force_fg set (or n_classes == 0) and counts is null does not read it at all.                                   */
+int msk_patch_select(msk_ctx* ctx, const int32_t* label, int d, int h, int w, int num_classes, const int32_t* classes,
+                     int n_classes, int rd, int rh, int rw, const uint32_t* words, int n_patches, void* workspace,
+                     int32_t* sel, int32_t* counts);
+/* dst [rd,rh,rw] = the patch of src [d,h,w] (4-byte elements, float32 or int32, copied as bits) whose origin is the first
+ * three words of ONE sel record, read on the device: dst[z][y][x] = src[d0+z][h0+y][w0+x] where that voxel exists, pad_bits
+ * where it does not.  16-byte stores where rw % 4 == 0, 16-byte loads where also w % 4 == 0 and w0 % 4 == 0.
+ * All three: integer arithmetic only, integer atomics for the totals only (results do not depend on scheduling); select and
+ * crop run asynchronously on the context stream, read their host arrays before they return, synchronise and download
+ * nothing, and nothing data-dependent can fail.  Argument errors, reported before any launch: null pointers, extents < 1,
+ * 2^31 voxels or more (volume or patch), num_classes outside 1..256, n_classes outside 0..32, a class that is not ascending
+ * or outside [0, num_classes), n_patches outside 1..16, dst overlapping src.                                                */
+int msk_patch_crop(msk_ctx* ctx, const void* src, int d, int h, int w, const int32_t* sel, void* dst, int rd, int rh, int rw,
+                   uint32_t pad_bits);
+
 /* ---- loss ------------------------------------------------------------------ */
 /* losses/loss_utils.py:31-40 class_weights: w_c = sum(1-softmax_c)/sum(softmax_c) */
 int msk_class_weights(msk_ctx* ctx, msk_tensor logits, float* weights);

@@ -134,6 +134,9 @@ SIGNATURES = {
     "msk_tta_finish": (_i, [_vp, _T, _i, _T, _vp]),
     "msk_sw_gather": (_i, [_vp, _T, _T, _vp, _f]),
     "msk_sw_accumulate": (_i, [_vp, _T, _vp, _vp, _i, _vp, _i, _vp, _i, _T]),
+    "msk_patch_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),
+    "msk_patch_select": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "msk_patch_crop": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _u32]),
     "msk_class_weights": (_i, [_vp, _T, _vp]),
     "msk_loss_fwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _vp]),
     "msk_loss_bwd": (_i, [_vp, _T, _vp, _vp, _i, _vp, _f, _f, _T]),

@@ -140,6 +140,53 @@ def connected_components_device(x, minimum_volume=0, k=0):
     return out
 
 
+def patch_select_device(label: DeviceVolume, roi, num_classes, classes, words) -> DeviceVolume:
+    """msk_patch_select: choose patch origins in a device label volume -> the ``sel`` records, an int32 ``DeviceVolume``
+    [n_patches, 8] (d0, h0, w0, cls, cz, cy, cx, 0) from the stream-ordered pool (``free()`` hands it back).
+
+    ``classes``: the strictly ascending candidate classes; ``words``: six 32-bit integers per patch (force_fg, w_cls, w_rank,
+    w_d, w_h, w_w), one patch or a sequence of up to 16.  The workspace comes from the pool and goes back to it (every later
+    op is enqueued behind this one on the same stream).  Nothing is downloaded and nothing synchronises: the host never learns
+    the origin.  With ``classes`` empty (or no patch forcing foreground) the volume is not read, so an image may stand in
+    for a missing label."""
+    dev = label.dev
+    d, h, w = label.shape
+    words = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).astype(np.uint32).reshape(-1, 6))
+    cls = np.ascontiguousarray(np.asarray(list(classes), dtype=np.int32).reshape(-1))
+    nbytes = C.c_size_t(0)
+    if dev.lib.msk_patch_workspace(C.c_long(d * h * w), int(num_classes), C.byref(nbytes)) != 0:
+        from ._lib import last_error
+        raise MskError("msk_patch_workspace failed: " + last_error(None))
+    sel = _pooled_volume(dev, (len(words), 8), np.int32)
+    ws = _pool_alloc(dev, nbytes.value)
+    try:
+        dev.call("msk_patch_select", C.c_void_p(label.ptr), d, h, w, int(num_classes), cls.ctypes.data_as(C.c_void_p), len(cls),
+                 int(roi[0]), int(roi[1]), int(roi[2]), words.ctypes.data_as(C.c_void_p), len(words), C.c_void_p(ws),
+                 C.c_void_p(sel.ptr), None)
+    except MskError:
+        sel.free()
+        raise
+    finally:
+        _pool_release(dev, ws, nbytes.value)
+    return sel
+
+
+def patch_crop_device(vol: DeviceVolume, sel: DeviceVolume, roi, pad=0, index=0) -> DeviceVolume:
+    """msk_patch_crop: the patch of ``vol`` at the origin of record ``index`` of ``sel`` (patch_select_device), read on the
+    device -> a pooled ``DeviceVolume`` of extent ``roi`` and vol's dtype; voxels outside the volume are ``pad``."""
+    if not 0 <= int(index) < sel.shape[0]:
+        raise ValueError("patch_crop_device: record {} of {}".format(index, sel.shape[0]))
+    out = _pooled_volume(vol.dev, roi, vol.dtype)
+    bits = int(np.array([pad], dtype=vol.dtype).view(np.uint32)[0])
+    try:
+        vol.dev.call("msk_patch_crop", C.c_void_p(vol.ptr), *vol.shape, C.c_void_p(sel.ptr + 32 * int(index)), C.c_void_p(out.ptr),
+                     int(roi[0]), int(roi[1]), int(roi[2]), C.c_uint32(bits))
+    except MskError:
+        out.free()
+        raise
+    return out
+
+
 def upload_pooled(image, dev=None) -> DeviceVolume:
     """Host volume -> pooled device buffer (loader path of the device augmentations)."""
     dev = dev or get_device()

@@ -1,2 +1,2 @@
-from .transform import (BinaryMaskToConnectComponent, Compose, RandomFlip3D, RandomResizedCrop3D, RandomRotation3D,
-                        Resize3D, TopkLargestConnectComponent)
+from .transform import (BinaryMaskToConnectComponent, Compose, RandomFlip3D, RandomPatchCrop3D, RandomResizedCrop3D,
+                        RandomRotation3D, Resize3D, TopkLargestConnectComponent)

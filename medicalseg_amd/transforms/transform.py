@@ -260,6 +260,110 @@ class RandomResizedCrop3D:
         return img, label
 
 
+def _patch_origin(roi, dim, pos=None, word=0):
+    """One axis of a patch origin: a volume no larger than the patch is centred (SlidingPlan's padding: (roi - dim) // 2
+    voxels in front); else the patch is centred on `pos` and pushed inside, or, without a centre, starts at
+    (word * (dim - roi + 1)) >> 32 -- word a 32-bit integer, so every start is hit and none lies outside."""
+    if dim <= roi:
+        return -((roi - dim) // 2)
+    if pos is None:
+        return (int(word) * (dim - roi + 1)) >> 32
+    return min(max(pos - roi // 2, 0), dim - roi)
+
+
+def _patch_select_host(label, roi, num_classes, classes, words):
+    """The patch record (d0, h0, w0, cls, cz, cy, cx, 0) msk_patch_select computes, from a host label (or None) and the six
+    words (force_fg, w_cls, w_rank, w_d, w_h, w_w); shape is the volume's when there is no label."""
+    force, w_cls, w_rank = int(words[0]), int(words[1]), int(words[2])
+    if force and label is not None and len(classes):
+        lab = np.asarray(label).reshape(-1)
+        inside = lab[(lab >= 0) & (lab < num_classes)]
+        counts = np.bincount(inside, minlength=num_classes)
+        present = [c for c in classes if counts[c] > 0]
+        if present:
+            cls = int(present[(w_cls * len(present)) >> 32])
+            r = (w_rank * int(counts[cls])) >> 32
+            centre = [int(v) for v in np.unravel_index(int(np.flatnonzero(lab == cls)[r]), label.shape)]
+            return [_patch_origin(ro, dim, c) for ro, dim, c in zip(roi, label.shape, centre)] + [cls] + centre + [0]
+    return None
+
+
+def _patch_crop_host(vol, origin, roi, pad):
+    out = np.full(tuple(roi), pad, dtype=vol.dtype)
+    src, dst = [], []
+    for o, ro, dim in zip(origin, roi, vol.shape):
+        lo, hi = max(o, 0), min(o + ro, dim)
+        src.append(slice(lo, hi))
+        dst.append(slice(lo - o, hi - o))
+    out[tuple(dst)] = vol[tuple(src)]
+    return out
+
+
+@manager.TRANSFORMS.add_component
+class RandomPatchCrop3D:
+    """A fixed-size patch cut at the volume's own resolution, the sampler patch-trained 3D nets use (nnU-Net, MONAI's
+    RandCropByPosNegLabel): with probability ``fg_prob`` the patch is centred on a voxel of a randomly chosen class of
+    ``classes`` that occurs in the label (every such class equally likely, every voxel of it equally likely), pushed inside the
+    volume; otherwise, and when there is no label or none of the classes occurs, its origin is uniform over the positions
+    inside the volume.  An axis shorter than the patch is centred and padded with ``pad_value`` (image) / ``label_pad``
+    (label).  Volumes of any size come out as ``size``, which is what batching needs.  Not in the reference.
+
+    ``classes=None`` means 1 .. num_classes - 1.  ``label_pad=255``, the datasets' ``ignore_index``, keeps the padding out of
+    the loss; the default 0 counts it as background.
+
+    Random stream: every call draws exactly one ``random.random()`` (the coin) and then five ``random.getrandbits(32)``
+    (class, rank, and one word per axis), whatever the data and the outcome, so the host and the device path cut the same
+    patch under the same seed.  On device volumes the choice is made by msk_patch_select on the device: the label is never
+    downloaded and nothing synchronises."""
+
+    def __init__(self, size, num_classes, fg_prob=1. / 3., classes=None, pad_value=0, label_pad=0):
+        if isinstance(size, int):
+            size = (size, size, size)
+        if not isinstance(size, (tuple, list)) or len(size) != 3 or any(int(s) < 1 for s in size):
+            raise ValueError("Size must be an int or three positive numbers, got {}.".format(size))
+        self.size = tuple(int(s) for s in size)
+        self.num_classes = int(num_classes)
+        if not 1 <= self.num_classes <= 256:
+            raise ValueError("num_classes must be in [1, 256], got {}.".format(num_classes))
+        self.fg_prob = float(fg_prob)
+        self.classes = list(range(1, self.num_classes)) if classes is None else [int(c) for c in classes]
+        if len(self.classes) > 32 or any(not 0 <= c < self.num_classes for c in self.classes) or \
+                any(b <= a for a, b in zip(self.classes, self.classes[1:])):
+            raise ValueError("classes must be at most 32 strictly ascending classes inside [0, num_classes), got {}.".format(classes))
+        self.pad_value = pad_value
+        self.label_pad = int(label_pad)
+
+    def get_params(self, have_label=True):
+        """the six words of msk_patch_select: force_fg, w_cls, w_rank, w_d, w_h, w_w"""
+        coin = random.random()
+        words = [random.getrandbits(32) for _ in range(5)]
+        return [int(have_label and coin < self.fg_prob)] + words
+
+    def select(self, shape, label, words):
+        """host path: the record (d0, h0, w0, cls, cz, cy, cx, 0)"""
+        rec = _patch_select_host(label, self.size, self.num_classes, self.classes, words)
+        if rec is None:
+            rec = [_patch_origin(ro, dim, None, w) for ro, dim, w in zip(self.size, shape, words[3:6])] + [-1, -1, -1, -1, 0]
+        return rec
+
+    def __call__(self, img, label=None):
+        words = self.get_params(label is not None)
+        if _on_device(img):
+            from ..preprocess import patch_crop_device, patch_select_device
+            sel = patch_select_device(img if label is None else label, self.size, self.num_classes,
+                                      [] if label is None else self.classes, words)
+            img = _swap(img, patch_crop_device(img, sel, self.size, self.pad_value))
+            if label is not None:
+                label = _swap(label, patch_crop_device(label, sel, self.size, self.label_pad))
+            sel.free()
+            return img, label
+        origin = self.select(img.shape[:3], label, words)[:3]
+        img = _patch_crop_host(img, origin, self.size, self.pad_value)
+        if label is not None:
+            label = _patch_crop_host(label, origin, self.size, self.label_pad)
+        return img, label
+
+
 def _connected_components(binary_mask, minimum_volume=0):
     """functional.py:117-131 (SimpleITK ConnectedComponent + RelabelComponent): face-connected
     components relabelled 1, 2, ... by decreasing size, components smaller than
