@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import bce_reference as R
-from helpers import dev, t_from_ncdhw, vec, vec_back, vp
+from helpers import dev, dmalloc, redzone_check, t_from_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,14 +37,14 @@ def _labels(rng, N, D, H, W, Cn, ignore_frac=0.1):
 
 def _device_labels(y):
     d = dev()
-    p = d.malloc(y.nbytes)
+    p = dmalloc(y.nbytes)
     d.h2d(p, y)
     return p
 
 
 def _fwd(zt, yp, weight, pos_weight):
     d = dev()
-    out, stats = vec(np.zeros(4)), d.malloc(8 * 8)
+    out, stats = vec(np.zeros(4)), dmalloc(8 * 8)
     pwm, pwv = _pw_args(pos_weight)
     d.call("msk_bce_fwd", zt.msk(), vp(yp), 255, MODES[weight], pwm, C.c_float(pwv), vp(out), vp(stats))
     return float(vec_back(out, 1)[0]), stats

@@ -6,7 +6,7 @@ Tolerances as in test_gpu_model.py (calibrated against the same oracle run in fl
 import numpy as np
 import pytest
 
-from helpers import dev, rel_err
+from helpers import dev, redzone_check, rel_err  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import dev, vec, vec_back, vp
+from helpers import dev, redzone_check, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 

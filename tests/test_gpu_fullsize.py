@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import dev, t_empty, t_from_ncdhw, vec, vec_back, vp
+from helpers import dev, dfree, redzone_check, t_empty, t_from_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,8 +32,8 @@ def test_conv5_128cubed_sampled_and_linear():
         xt, yt = t_from_ncdhw(x), t_empty(1, Cc, S, S, S)
         d.call("msk_conv3d_fwd", desc, xt.msk(), vp(wp), vp(bp) if bias else None, yt.msk())
         out = yt.numpy()
-        d.free(xt.ptr)
-        d.free(yt.ptr)
+        dfree(xt.ptr)
+        dfree(yt.ptr)
         return out
 
     y1 = conv(x1)

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import fullsize_cases as FC
-from helpers import dev
+from helpers import dev, redzone_check  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))

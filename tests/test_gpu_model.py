@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import dev, rel_err
+from helpers import dev, redzone_check, rel_err  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 

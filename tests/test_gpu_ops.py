@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import dev, rel_err, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp
+from helpers import dev, dfree, dmalloc, redzone_check, rel_err, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -294,9 +294,11 @@ def test_conv_strided_channel_slice():
     w = (rng.standard_normal((32, 32, 5, 5, 5)) / 60).astype(np.float32)
     y_ref = O.conv3d(x.astype(np.float64), w.astype(np.float64), None, 1, 2)
     xt = t_from_ncdhw(x, ld=48)
-    yt = t_empty(1, 32, 4, 6, 33, ld=40, fill=0.0)
+    yt = t_empty(1, 32, 4, 6, 33, ld=40, fill=-3.0)
     d.call("msk_conv3d_fwd", _desc((5,) * 3, (1,) * 3, (2,) * 3), xt.msk(), vp(vec(w.ravel())), None, yt.msk())
     assert rel_err(yt.numpy(), y_ref) < 5e-5
+    raw = vec_back(yt.ptr, 4 * 6 * 33 * 40).reshape(-1, 40)
+    assert np.all(raw[:, 32:] == -3.0)      # channels 32..39 of the wider buffer survive
 
 
 @pytest.mark.parametrize("C_,shape", [(16, (2, 9, 10, 11)), (3, (1, 7, 8, 9)), (256, (2, 4, 4, 4)), (20, (1, 5, 6, 7)),
@@ -400,7 +402,7 @@ def test_copy_scale_channel_sum_argmax_layout():
     out = vec(np.ones(20))
     d.call("msk_channel_sum", xt.msk(), vp(out), 1)
     assert rel_err(vec_back(out, 20), x.sum(axis=(0, 2, 3, 4)) + 1.0) < 1e-5
-    am = d.malloc(2 * 3 * 5 * 4 * 4)
+    am = dmalloc(2 * 3 * 5 * 4 * 4)
     d.call("msk_argmax_c", xt.msk(), vp(am))
     assert np.array_equal(d.d2h(am, (2, 3, 5, 4), np.int32), x.argmax(axis=1))
     assert np.array_equal(xt.numpy(), x)  # NDHWC -> NCDHW round trip
@@ -418,13 +420,13 @@ def test_loss_fwd_bwd(ncls, shape):
     y = rng.integers(0, ncls, (N, D, H, W)).astype(np.int32)
     y[0, 0, 0, :2] = 255  # ignore_index voxels (CE only)
     zt = t_from_ncdhw(z)
-    yp = d.malloc(y.nbytes)
+    yp = dmalloc(y.nbytes)
     d.h2d(yp, y)
     wv = vec(np.zeros(ncls))
     d.call("msk_class_weights", zt.msk(), vp(wv))
     w_ref = O.class_weights(z.astype(np.float64))
     assert rel_err(vec_back(wv, ncls), w_ref) < 1e-5
-    out, stats = vec(np.zeros(2 + ncls)), d.malloc((3 * ncls + 2) * 8)
+    out, stats = vec(np.zeros(2 + ncls)), dmalloc((3 * ncls + 2) * 8)
     d.call("msk_loss_fwd", zt.msk(), vp(yp), vp(wv), 255, vp(out), vp(stats))
     ce_ref, dce = O.cross_entropy(z.astype(np.float64), y, w_ref, 255)
     ysafe = np.where(y == 255, 0, y)
@@ -452,12 +454,12 @@ def test_loss_known_answer():
     z = rng.standard_normal((1, 3, 2, 3, 4)).astype(np.float32)
     y = rng.integers(0, 3, (1, 2, 3, 4)).astype(np.int32)
     zt = t_from_ncdhw(z)
-    yp = d.malloc(y.nbytes)
+    yp = dmalloc(y.nbytes)
     d.h2d(yp, y)
     wv = vec(np.zeros(3))
     d.call("msk_class_weights", zt.msk(), vp(wv))
     assert np.allclose(vec_back(wv, 3), [2.47594326, 1.75639001, 1.86110799], rtol=2e-6)
-    out, stats = vec(np.zeros(5)), d.malloc(11 * 8)
+    out, stats = vec(np.zeros(5)), dmalloc(11 * 8)
     d.call("msk_loss_fwd", zt.msk(), vp(yp), vp(wv), 255, vp(out), vp(stats))
     o = vec_back(out, 5)
     assert abs(o[0] - 1.4261519761109072) < 3e-6
@@ -516,13 +518,13 @@ def test_dice_options(ncls, shape, sigmoid_norm, weighted):
     z = (rng.standard_normal((N, ncls, D, H, W)) * 2).astype(np.float32)
     y = rng.integers(0, ncls, (N, D, H, W)).astype(np.int32)
     zt = t_from_ncdhw(z)
-    yp = d.malloc(y.nbytes)
+    yp = dmalloc(y.nbytes)
     d.h2d(yp, y)
     w_ce = O.class_weights(z.astype(np.float64))
     wv = vec(w_ce)
     dw = rng.uniform(0.5, 2.0, ncls) if weighted else None
     dwp = vec(dw) if weighted else None
-    out, stats = vec(np.zeros(2 + ncls)), d.malloc((3 * ncls + 2) * 8)
+    out, stats = vec(np.zeros(2 + ncls)), dmalloc((3 * ncls + 2) * 8)
     d.call("msk_loss_fwd_ex", zt.msk(), vp(yp), vp(wv), 255, int(not sigmoid_norm), vp(dwp) if weighted else None,
            vp(out), vp(stats))
     z64 = z.astype(np.float64)
@@ -586,7 +588,7 @@ def test_interp_trilinear_fwd_bwd(case):
     dxt = t_empty(N, Cn, sd, sh, sw, fill=1.0)
     need = C.c_size_t(0)
     d.call("msk_interp_scratch_bytes", dxt.msk(), gt.msk(), C.byref(need))
-    scratch = d.malloc(max(need.value, 16))
+    scratch = dmalloc(max(need.value, 16))
     d.call("msk_interp_trilinear_bwd", gt.msk(), dxt.msk(), 0, vp(scratch), C.c_size_t(need.value))
     assert rel_err(t_to_ncdhw(dxt), dx_ref) < 1e-5
     d.call("msk_interp_trilinear_bwd", gt.msk(), dxt.msk(), 1, vp(scratch), C.c_size_t(need.value))
@@ -1149,7 +1151,7 @@ def test_out_tr_amax_travels_in_xform_header():
     xt, dyt, wp, bp = t_from_ncdhw(x), t_from_ncdhw(dy), vec(w.ravel()), vec(b)
     nbytes = int(d.lib.msk_conv3d_xform_bytes(d.ctx, _desc(k, s_, p), xt.msk(), 3))
     assert nbytes == 512
-    xf = d.malloc(nbytes)
+    xf = dmalloc(nbytes)
     yt = t_empty(N, 3, D, H, W)
     d.call("msk_conv3d_fwd_ex", _desc(k, s_, p), xt.msk(), vp(wp), vp(bp), yt.msk(), None, C.c_void_p(xf))
     amax = d.d2h(xf, (64,), np.float32)
@@ -1192,7 +1194,7 @@ def test_tile_staged_records_equal_the_direct_form_bitwise():
     from medicalseg_amd._lib import MskConvDesc
     cd = MskConvDesc(1, 1, 1, 1, 1, 1, 0, 0, 0)
     zt = t_from_ncdhw(z)
-    yp = d.malloc(y.nbytes)
+    yp = dmalloc(y.nbytes)
     d.h2d(yp, y)
     wp, bp = vec(w.ravel()), vec(b)
     res = {}
@@ -1207,7 +1209,7 @@ def test_tile_staged_records_equal_the_direct_form_bitwise():
             d.prof_enable(False)
             assert d.prof_report().get("pointwise_mid", (0, 0))[0] == 2
             wv = vec(np.ones(ncls))
-            out, stats = vec(np.zeros(2 + ncls)), d.malloc((3 * ncls + 2) * 8)
+            out, stats = vec(np.zeros(2 + ncls)), dmalloc((3 * ncls + 2) * 8)
             d.call("msk_loss_fwd", lt.msk(), vp(yp), vp(wv), 255, vp(out), vp(stats))
             dz = t_empty(N, ncls, D, H, W, fill=9.0)
             d.call("msk_loss_bwd", lt.msk(), vp(yp), vp(wv), 255, vp(stats), C.c_float(1.0), C.c_float(1.0), dz.msk())
@@ -1294,7 +1296,7 @@ def test_small_pack_cache_follows_every_weight_write():
                C.c_float(1e-8), C.c_double(0.9), C.c_double(0.999), C.c_float(0.0), C.c_float(1.0))
         w_adam = d.d2h(wp, (cout, cin) + k, np.float32)
         check(wp, w_adam, "after adam")
-        d.free(wp)
+        dfree(wp)
         w5 = mkw(5.0)
         wp2 = vec(w5.ravel())
         check(wp2, w5, "after free + malloc")

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import dev, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp
+from helpers import dev, redzone_check, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 K5, S1, P2 = (5, 5, 5), (1, 1, 1), (2, 2, 2)
 CJ = 32

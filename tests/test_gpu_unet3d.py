@@ -3,6 +3,8 @@ logits, the CE+Dice loss, every parameter gradient, and a training step through 
 import numpy as np
 import pytest
 
+from helpers import redzone_check  # noqa: F401 (autouse)
+
 pytestmark = pytest.mark.gpu
 
 

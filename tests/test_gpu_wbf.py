@@ -10,7 +10,7 @@ import pytest
 
 import ctypes as C
 
-from helpers import dev, rel_err, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp
+from helpers import dev, dfree, dmalloc, redzone_check, rel_err, t_empty, t_from_ncdhw, t_to_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -218,7 +218,7 @@ def test_conv3d_fwd_ex_stats_and_kept_transform(case):
     stats = vec(np.zeros(2 * cout, np.float32))
     nbytes = int(d.lib.msk_conv3d_xform_bytes(d.ctx, _desc(k, s_, p), xt.msk(), cout))
     assert (nbytes > 0) == (cin >= 32)
-    xf = d.malloc(nbytes) if nbytes else None
+    xf = dmalloc(nbytes) if nbytes else None
     d.set_option("wgrad_async", 0)
     try:
         d.call("msk_conv3d_fwd_ex", _desc(k, s_, p), xt.msk(), vp(wp), vp(bp), yt.msk(), vp(stats), vp(xf))
@@ -352,8 +352,8 @@ def test_conv3d_bwd_bnact_fused_equals_three_call_form(case, split):
     nx = int(d.lib.msk_conv3d_xform_bytes(d.ctx, desc, xt.msk(), c))
     nb = int(d.lib.msk_conv3d_bwd_bnact_bytes(d.ctx, desc, xt.msk(), yt.msk()))
     assert (nb > 0) == (c >= 32) and (nx > 0) == (c >= 32)
-    xf = d.malloc(nx) if nx else None
-    ybuf = d.malloc(nb) if nb else None
+    xf = dmalloc(nx) if nx else None
+    ybuf = dmalloc(nb) if nb else None
     ytmp = t_empty(N, c, D, H, W, fill=0.0)
     d.call("msk_conv3d_fwd_ex", desc, xt.msk(), vp(wp), vp(bp), ytmp.msk(), None, vp(xf))   # fills xf for x
     # the reduce pass the backward always starts with: its maxima bound |dy| (needed by the fused forms under split 2)
@@ -747,7 +747,7 @@ def test_wbf_packed_weight_cache_follows_every_weight_write():
     assert np.abs(w_adam - (w1 - 0.5 * g)).max() > 1e-3
     check(wp, w_adam, "after adam")
     # free + a new allocation (very likely at the same address) with other weights
-    d.free(wp)
+    dfree(wp)
     w5 = mkw(5.0)
     wp2 = vec(w5.ravel())
     check(wp2, w5, "after free + malloc")
@@ -788,7 +788,7 @@ def test_wbf_packed_weight_cache_free_of_an_arena_and_foreign_writes():
 
     # (a) weights at an offset inside an "arena"
     off = 4096
-    arena = d.malloc(off * 4 + count * 4 + 1024)
+    arena = d.malloc(off * 4 + count * 4 + 1024)           # unguarded on purpose: msk_free of THIS allocation is what is tested
     w1 = mkw(1.0)
     d.h2d(arena + off * 4, w1.ravel())
     assert err(arena + off * 4, w1) < _conv_tol(cin * 125)
@@ -1213,10 +1213,10 @@ def test_pipelined_one_kernel_matrix_stage_is_bitwise_reproducible(c, size):
     n = 2
     vox = n * size ** 3
     from medicalseg_amd.device import Tensor
-    mk = lambda: Tensor(d, d.malloc(vox * c * 4), n, size, size, size, c, c, None)
+    mk = lambda: Tensor(d, dmalloc(vox * c * 4), n, size, size, size, c, c, None)
     x, y, dx = mk(), mk(), mk()
     d.h2d(x.ptr, rng.standard_normal(vox * c, dtype=np.float32))
-    w = d.malloc(c * c * 125 * 4)
+    w = dmalloc(c * c * 125 * 4)
     d.h2d(w, (rng.standard_normal(c * c * 125) * 0.01).astype(np.float32))
     b = d.small(c)
     cd = _desc((5, 5, 5), (1, 1, 1), (2, 2, 2))
@@ -1235,8 +1235,8 @@ def test_pipelined_one_kernel_matrix_stage_is_bitwise_reproducible(c, size):
         d.prof_enable(False)
         d.set_option("prof_shapes", 0)
         for t in (x, y, dx):
-            d.free(t.ptr)
-        d.free(w)
+            dfree(t.ptr)
+        dfree(w)
     tags = d.prof_report()
     assert any(k.startswith("wbf_gemm_h2_k") and "fused" in k for k in tags), sorted(tags)
     assert len(hashes) == 1, "results differ between runs: %d distinct" % len(hashes)
