@@ -499,6 +499,48 @@ int msk_patch_select(msk_ctx* ctx, const int32_t* label, int d, int h, int w, in
 int msk_patch_crop(msk_ctx* ctx, const void* src, int d, int h, int w, const int32_t* sel, void* dst, int rd, int rh, int rw,
                    uint32_t pad_bits);
 
+/* ---- intensity augmentation (transforms.RandomGaussianNoise3D / RandomGaussianBlur3D / RandomBrightness3D /
+ *      RandomContrast3D / RandomGamma3D; no reference call site: the reference has geometric augmentation only) ---- */
+#define MSK_INTENSITY_NOISE 0
+#define MSK_INTENSITY_SCALE 1
+#define MSK_INTENSITY_CONTRAST 2
+#define MSK_INTENSITY_GAMMA 3
+#define MSK_INTENSITY_RESTORE 4
+/* Bytes of workspace msk_intensity_stats needs for a volume of n voxels (in [1, 2^31)): 24 bytes per chunk of 4096 voxels.
+ * Needs no context and no GPU.                                                                                               */
+int msk_intensity_stats_workspace(long n, size_t* bytes);
+/* stats (DEVICE, 4 doubles, 8-byte aligned) = {min, max, sum, sumsq} of the n float32 of x (DEVICE, 4-byte aligned; finite),
+ * as tests/intensity_reference.py states it: min and max exact; sum and sumsq in float64 in a FIXED order -- chunk c covers
+ * the voxels [4096c, 4096(c+1)), lane l of 256 adds x[l], x[l+256], ..., x[l+3840] in ascending order (elements past n add
+ * +0.0), sumsq adds the exact (double)x * (double)x, the 256 lane values are combined by the tree v[l] += v[l+s], s = 128,
+ * 64, ..., 1, and the chunk values are reduced by the same scheme (lane l adds P[l], P[l+256], ..., then the tree).  Two
+ * launches on the context stream, no atomics, no synchronisation, no download.  workspace (DEVICE): 8-byte aligned,
+ * msk_intensity_stats_workspace bytes; its contents mean nothing to the caller.                                              */
+int msk_intensity_stats(msk_ctx* ctx, const float* x, long n, void* workspace, double* stats);
+/* One streaming pass y[i] = f(x[i]) over n float32 (DEVICE, 4-byte aligned; 16 bytes per lane where both are 16-byte aligned;
+ * y == x is allowed, any other overlap is an error).  params: HOST array of 4 floats, read before the call returns.  stats_a /
+ * stats_b: DEVICE records of msk_intensity_stats, read on the device (nothing synchronises); a mode that does not use one
+ * accepts null.  Every float operation is rounded on its own (no FMA).  mode:
+ *   NOISE     y = x + p0 * z_i;  k = splitmix64(seed), h = splitmix64(k + i), u1 = ((h >> 40) + 1) * 2^-24,
+ *             u2 = ((h >> 8) & 0xFFFFFF) * 2^-24, z = sqrtf(-2 logf(u1)) * cosf(2 pi u2)
+ *   SCALE     y = x * p0
+ *   CONTRAST  (stats_a) m = (float)(sum_a / n);  y = ((x - m) * p0) + m, clamped to [(float)min_a, (float)max_a] if p1 != 0
+ *   GAMMA     (stats_a) s = p1 != 0 ? -1 : 1;  (mn, mx) = s > 0 ? (min_a, max_a) : (-max_a, -min_a);  rg = mx - mn;
+ *             y = s * (powf((s * x - mn) / (rg + 1e-7f), p0) * rg + mn)
+ *   RESTORE   (stats_a of the volume before, stats_b of x) mean = sum / n, sd = sqrt(max(sumsq / n - mean * mean, 0)) in
+ *             float64, rounded to float32;  y = (x - mean_b) / (sd_b + 1e-8f) * sd_a + mean_a                                 */
+int msk_intensity_apply(msk_ctx* ctx, const float* x, float* y, long n, int mode, const float* params, const double* stats_a,
+                        const double* stats_b, uint64_t seed);
+/* y [d,h,w] = x blurred along d, then h, then w with HOST taps of 2r+1 floats per axis (r in 0..8; r == 0 skips the axis, all
+ * three 0 copy) and scipy's mode='reflect': per pass out[i] = sum over k = -r..r ascending of w[k] * in[reflect(i + k)], a
+ * float32 multiply then a float32 add, starting from the first product;  reflect(i) = m < n ? m : 2n-1-m, m = i mod 2n >= 0
+ * (any extent >= 1).  y must not overlap x; tmp (DEVICE, d*h*w floats, overlapping neither) is needed when two or three axes
+ * are blurred.  Up to three launches on the context stream, no atomics.  Argument errors of all four, reported before any
+ * launch: null or misaligned pointers, n or d*h*w outside [1, 2^31), an unknown mode, a missing record, r outside 0..8,
+ * overlapping buffers.                                                                                                       */
+int msk_gauss_blur3d(msk_ctx* ctx, const float* x, float* y, int d, int h, int w, const float* taps_d, int r_d,
+                     const float* taps_h, int r_h, const float* taps_w, int r_w, float* tmp);
+
 /* ---- loss ------------------------------------------------------------------ */
 /* losses/loss_utils.py:31-40 class_weights: w_c = sum(1-softmax_c)/sum(softmax_c) */
 int msk_class_weights(msk_ctx* ctx, msk_tensor logits, float* weights);

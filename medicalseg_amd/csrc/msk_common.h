@@ -318,6 +318,14 @@ __device__ __forceinline__ void msk_tile_store(float* __restrict__ dst, int nqua
   }
 }
 
+// splitmix64: the word of the counter RNGs (Dropout3D masks in msk_elementwise.hip, Gaussian noise in msk_intensity.hip)
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ float msk_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

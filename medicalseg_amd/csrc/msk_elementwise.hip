@@ -891,13 +891,7 @@ channel_sum_partial_k(const float* __restrict__ x, int ldx, long voxels, int C, 
   if (vl == 0) partial[((long)blockIdx.y * nb + blockIdx.x) * CB + cl] = sh[t];
 }
 
-// splitmix64-based counter RNG for Dropout3D masks
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// counter RNG for Dropout3D masks (splitmix64: msk_common.h)
 __global__ void dropout_mask_k(uint64_t seed, uint64_t step, uint32_t site, int count, float p, float* mask) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;

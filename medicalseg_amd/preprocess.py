@@ -14,7 +14,8 @@ from .device import get_device
 
 
 class DeviceVolume:
-    """A 3-D float32/int32 volume on the device (persistent allocation)."""
+    """A 3-D float32/int32 volume on the device (persistent allocation); also the small records device ops hand to each
+    other (int32 patch records, float64 intensity statistics)."""
 
     def __init__(self, dev, ptr, shape, dtype):
         self.dev, self.ptr, self.shape, self.dtype = dev, ptr, tuple(int(s) for s in shape), np.dtype(dtype)
@@ -30,7 +31,7 @@ class DeviceVolume:
     def free(self):
         if self.ptr:
             if self.pooled:
-                _pool_release(self.dev, self.ptr, self.size * 4)
+                _pool_release(self.dev, self.ptr, self.size * self.dtype.itemsize)
             else:
                 self.dev.free(self.ptr)
             self.ptr = None
@@ -53,7 +54,7 @@ def _pool_release(dev, ptr, nbytes):
 
 def _pooled_volume(dev, shape, dtype) -> DeviceVolume:
     shape = tuple(int(v) for v in shape)
-    v = DeviceVolume(dev, _pool_alloc(dev, int(np.prod(shape)) * 4), shape, dtype)
+    v = DeviceVolume(dev, _pool_alloc(dev, int(np.prod(shape)) * np.dtype(dtype).itemsize), shape, dtype)
     v.pooled = True
     return v
 
@@ -184,6 +185,103 @@ def patch_crop_device(vol: DeviceVolume, sel: DeviceVolume, roi, pad=0, index=0)
     except MskError:
         out.free()
         raise
+    return out
+
+
+INTENSITY_NOISE, INTENSITY_SCALE, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_RESTORE = range(5)   # MSK_INTENSITY_*
+GAUSS_MAX_SIGMA = 2.0   # radius int(4 sigma + 0.5) <= 8, the widest msk_gauss_blur3d takes
+
+
+def gauss_taps(sigma) -> np.ndarray:
+    """The 2r+1 float32 weights of one blurred axis, r = int(4 sigma + 0.5) (scipy.ndimage.gaussian_filter's kernel at
+    truncate 4, computed in float64 and rounded once); empty when r == 0.  The host path and the device path of the blur use
+    these same numbers."""
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= GAUSS_MAX_SIGMA:
+        raise ValueError("sigma must be in [0, {}], got {}".format(GAUSS_MAX_SIGMA, sigma))
+    r = int(4.0 * sigma + 0.5)
+    if r == 0:
+        return np.zeros(0, np.float32)
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (sigma * sigma) * k * k)
+    return (w / w.sum()).astype(np.float32)
+
+
+def _float_volume(vol, what):
+    if not isinstance(vol, DeviceVolume) or vol.dtype != np.float32:
+        raise TypeError("{} takes a float32 DeviceVolume".format(what))
+
+
+def intensity_stats_device(vol: DeviceVolume) -> DeviceVolume:
+    """msk_intensity_stats: the record {min, max, sum, sumsq} of a float32 volume as four float64 in a pooled device buffer
+    (a ``DeviceVolume`` of shape (4,), ``free()`` hands it back), in the fixed summation order of tests/intensity_reference.py.
+    The workspace comes from the pool and goes back to it (every later op is enqueued behind this one on the same stream).
+    Nothing is downloaded and nothing synchronises: the record is read by msk_intensity_apply on the device."""
+    _float_volume(vol, "intensity_stats_device")
+    dev = vol.dev
+    nbytes = C.c_size_t(0)
+    if dev.lib.msk_intensity_stats_workspace(C.c_long(vol.size), C.byref(nbytes)) != 0:
+        from ._lib import last_error
+        raise MskError("msk_intensity_stats_workspace failed: " + last_error(None))
+    rec = _pooled_volume(dev, (4,), np.float64)
+    ws = _pool_alloc(dev, nbytes.value)
+    try:
+        dev.call("msk_intensity_stats", C.c_void_p(vol.ptr), C.c_long(vol.size), C.c_void_p(ws), C.c_void_p(rec.ptr))
+    except MskError:
+        rec.free()
+        raise
+    finally:
+        _pool_release(dev, ws, nbytes.value)
+    return rec
+
+
+def intensity_apply_device(vol: DeviceVolume, mode, params, stats_a=None, stats_b=None, seed=0, inplace=True) -> DeviceVolume:
+    """msk_intensity_apply: one streaming pass over a float32 volume, in place (returns ``vol``) or into a new pooled volume.
+    ``mode``: INTENSITY_NOISE (params: std; ``seed``), INTENSITY_SCALE (factor), INTENSITY_CONTRAST (factor, preserve_range;
+    ``stats_a``), INTENSITY_GAMMA (gamma, invert; ``stats_a``), INTENSITY_RESTORE (``stats_a`` of the volume before,
+    ``stats_b`` of ``vol``).  The records are intensity_stats_device's and are read on the device: nothing synchronises."""
+    _float_volume(vol, "intensity_apply_device")
+    p = np.zeros(4, np.float32)
+    params = np.asarray(params, np.float32).reshape(-1)
+    p[:params.size] = params
+    out = vol if inplace else _pooled_volume(vol.dev, vol.shape, vol.dtype)
+    try:
+        vol.dev.call("msk_intensity_apply", C.c_void_p(vol.ptr), C.c_void_p(out.ptr), C.c_long(vol.size), int(mode),
+                     p.ctypes.data_as(C.c_void_p), C.c_void_p(stats_a.ptr) if stats_a is not None else None,
+                     C.c_void_p(stats_b.ptr) if stats_b is not None else None, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF))
+    except MskError:
+        if out is not vol:
+            out.free()
+        raise
+    return out
+
+
+def gauss_blur_device(vol: DeviceVolume, sigma) -> DeviceVolume:
+    """msk_gauss_blur3d: separable Gaussian blur (scipy's mode='reflect', truncate 4) of a float32 volume into a new pooled
+    volume; ``sigma`` a scalar or one value per axis (D, H, W), 0 skips an axis, at most 2.  The scratch volume comes from the
+    pool and goes back to it."""
+    _float_volume(vol, "gauss_blur_device")
+    if len(vol.shape) != 3:
+        raise ValueError("expected a 3-D volume, got shape {}".format(vol.shape))
+    sig = [float(sigma)] * 3 if np.isscalar(sigma) else [float(s) for s in sigma]
+    if len(sig) != 3:
+        raise ValueError("sigma must be a scalar or three values, got {}".format(sigma))
+    taps = [gauss_taps(s) for s in sig]
+    dev = vol.dev
+    out = _pooled_volume(dev, vol.shape, vol.dtype)
+    nbytes = vol.size * 4
+    tmp = _pool_alloc(dev, nbytes) if sum(len(t) > 0 for t in taps) >= 2 else None
+    args = []
+    for t in taps:
+        args += [t.ctypes.data_as(C.c_void_p) if len(t) else None, (len(t) - 1) // 2 if len(t) else 0]
+    try:
+        dev.call("msk_gauss_blur3d", C.c_void_p(vol.ptr), C.c_void_p(out.ptr), *vol.shape, *args, C.c_void_p(tmp) if tmp else None)
+    except MskError:
+        out.free()
+        raise
+    finally:
+        if tmp:
+            _pool_release(dev, tmp, nbytes)
     return out
 
 

@@ -364,6 +364,287 @@ class RandomPatchCrop3D:
         return img, label
 
 
+# ---- intensity augmentation (nnU-Net / batchgenerators' set; not in the reference) -----------------------------------------
+# Host paths: numpy evaluations of tests/intensity_reference.py's statement, float32 throughout.  Device paths: msk_intensity.hip
+# through preprocess.intensity_stats_device / intensity_apply_device / gauss_blur_device; the statistics stay on the device.
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _lanes_then_tree(terms):
+    """float64 [groups, k, 256] -> [groups]: lane l adds its k terms in order, then the tree v[l] += v[l+s], s = 128 .. 1"""
+    acc = np.zeros((terms.shape[0], 256), np.float64)
+    for j in range(terms.shape[1]):
+        acc = acc + terms[:, j, :]
+    s = 128
+    while s >= 1:
+        acc = acc[:, :s] + acc[:, s:2 * s]
+        s //= 2
+    return acc[:, 0]
+
+
+def _ordered_sum(v):
+    """msk_intensity_stats' float64 sum: chunks of 4096 (256 lanes x 16 strided terms, then the tree), then the chunk values
+    by the same scheme; missing elements count as +0.0"""
+    nc = -(-v.size // 4096)
+    pad = np.zeros(nc * 4096, np.float64)
+    pad[:v.size] = v
+    p = _lanes_then_tree(pad.reshape(nc, 16, 256))
+    rows = -(-nc // 256)
+    pad = np.zeros(rows * 256, np.float64)
+    pad[:nc] = p
+    return float(_lanes_then_tree(pad.reshape(1, rows, 256))[0])
+
+
+def _stats_host(x):
+    """the record {min, max, sum, sumsq} of msk_intensity_stats, bit for bit"""
+    d = np.asarray(x, np.float32).reshape(-1).astype(np.float64)
+    return np.array([d.min(), d.max(), _ordered_sum(d), _ordered_sum(d * d)], np.float64)
+
+
+def _splitmix64(z):
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _noise_host(x, std, seed):
+    x = np.asarray(x, np.float32)
+    with np.errstate(over="ignore"):
+        h = _splitmix64(_splitmix64(np.uint64(int(seed) & _MASK64)) + np.arange(x.size, dtype=np.uint64))
+    u1 = ((h >> np.uint64(40)) + np.uint64(1)).astype(np.float32) * np.float32(2.0 ** -24)
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float32) * np.float32(2.0 ** -24)
+    z = np.sqrt(np.float32(-2.0) * np.log(u1)) * np.cos(np.float32(2.0 * np.pi) * u2)
+    return x + np.float32(std) * z.reshape(x.shape)
+
+
+def _contrast_host(x, factor, preserve_range):
+    x = np.asarray(x, np.float32)
+    rec = _stats_host(x)
+    m = np.float32(rec[2] / np.float64(x.size))
+    y = ((x - m) * np.float32(factor)) + m
+    if preserve_range:
+        y = np.minimum(np.maximum(y, np.float32(rec[0])), np.float32(rec[1]))
+    return y
+
+
+def _gamma_host(x, gamma, invert, rec):
+    x = np.asarray(x, np.float32)
+    s = np.float32(-1.0 if invert else 1.0)
+    mn, mx = (-np.float32(rec[1]), -np.float32(rec[0])) if invert else (np.float32(rec[0]), np.float32(rec[1]))
+    rg = mx - mn
+    return s * (np.power((s * x - mn) / (rg + np.float32(1e-7)), np.float32(gamma)) * rg + mn)
+
+
+def _moments(rec, n):
+    mean = rec[2] / np.float64(n)
+    var = max(rec[3] / np.float64(n) - mean * mean, 0.0)
+    return np.float32(mean), np.float32(np.sqrt(var))
+
+
+def _restore_host(x, rec_a, rec_b):
+    mean_a, sd_a = _moments(rec_a, x.size)
+    mean_b, sd_b = _moments(rec_b, x.size)
+    return (x - mean_b) / (sd_b + np.float32(1e-8)) * sd_a + mean_a
+
+
+def _blur_host(x, sigmas):
+    from ..preprocess import gauss_taps
+    y = np.asarray(x, np.float32)
+    for axis, sigma in enumerate(sigmas):
+        w = gauss_taps(sigma)
+        if not len(w):
+            continue
+        r, n = (len(w) - 1) // 2, y.shape[axis]
+        acc = None
+        for k in range(-r, r + 1):
+            m = np.mod(np.arange(n) + k, 2 * n)
+            term = w[k + r] * np.take(y, np.where(m < n, m, 2 * n - 1 - m), axis=axis)
+            acc = term if acc is None else acc + term
+        y = acc
+    return y
+
+
+def _check_prob(prob):
+    prob = float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("prob must be in [0, 1], got {}.".format(prob))
+    return prob
+
+
+def _check_range(rng, name, lowest=None, highest=None):
+    if isinstance(rng, numbers.Number):
+        rng = (rng, rng)
+    if not isinstance(rng, (tuple, list)) or len(rng) != 2:
+        raise ValueError("{} must be a (low, high) pair, got {}.".format(name, rng))
+    lo, hi = float(rng[0]), float(rng[1])
+    if not lo <= hi or (lowest is not None and lo < lowest) or (highest is not None and hi > highest):
+        raise ValueError("{} must be an ordered range inside [{}, {}], got {}.".format(name, lowest, highest, rng))
+    return (lo, hi)
+
+
+def _value(rng, u):
+    return rng[0] + (rng[1] - rng[0]) * u
+
+
+def _branch_value(rng, coin, u):
+    """batchgenerators' draw for contrast and gamma: below 1 on one side of the coin, above on the other"""
+    lo, hi = rng
+    return _value((lo, 1.0) if coin < 0.5 and lo < 1 else (max(lo, 1.0), hi), u)
+
+
+@manager.TRANSFORMS.add_component
+class RandomGaussianNoise3D:
+    """With probability ``prob``: image + std * z, z standard normal from the counter RNG of msk_intensity_apply (splitmix64 of
+    the voxel's raster index, Box-Muller), std uniform in ``std``.  The label passes through.  Not in the reference.
+
+    Random stream, whatever the coin: ``random.random()`` (coin), ``random.random()`` (std), ``random.getrandbits(64)``."""
+
+    def __init__(self, prob=0.1, std=(0.0, 0.1)):
+        self.prob = _check_prob(prob)
+        self.std = _check_range(std, "std", lowest=0.0)
+
+    def get_params(self):
+        coin, u, seed = random.random(), random.random(), random.getrandbits(64)
+        return coin < self.prob, float(np.float32(_value(self.std, u))), seed
+
+    def __call__(self, img, label=None):
+        fire, std, seed = self.get_params()
+        if fire:
+            if _on_device(img):
+                from ..preprocess import INTENSITY_NOISE, intensity_apply_device
+                intensity_apply_device(img, INTENSITY_NOISE, [std], seed=seed)
+            else:
+                img = _noise_host(img, std, seed)
+        return img, label
+
+
+@manager.TRANSFORMS.add_component
+class RandomGaussianBlur3D:
+    """With probability ``prob``: a separable Gaussian blur (scipy's mode='reflect', truncate 4), sigma uniform in ``sigma``
+    (at most 2), one value for all axes or, with ``per_axis``, one per axis.  The label passes through.  Not in the reference.
+
+    Random stream, whatever the coin: ``random.random()`` (coin) and three more; without ``per_axis`` the first of the three
+    sets every axis."""
+
+    def __init__(self, prob=0.2, sigma=(0.5, 1.0), per_axis=False):
+        from ..preprocess import GAUSS_MAX_SIGMA
+        self.prob = _check_prob(prob)
+        self.sigma = _check_range(sigma, "sigma", lowest=0.0, highest=GAUSS_MAX_SIGMA)
+        self.per_axis = bool(per_axis)
+
+    def get_params(self):
+        coin = random.random()
+        u = [random.random() for _ in range(3)]
+        if not self.per_axis:
+            u = [u[0]] * 3
+        return coin < self.prob, [_value(self.sigma, v) for v in u]
+
+    def __call__(self, img, label=None):
+        fire, sigmas = self.get_params()
+        if fire:
+            if _on_device(img):
+                from ..preprocess import gauss_blur_device
+                img = _swap(img, gauss_blur_device(img, sigmas))
+            else:
+                img = _blur_host(img, sigmas)
+        return img, label
+
+
+@manager.TRANSFORMS.add_component
+class RandomBrightness3D:
+    """With probability ``prob``: image * factor, factor uniform in ``factor`` (nnU-Net's multiplicative brightness).  The
+    label passes through.  Not in the reference.  Random stream, whatever the coin: ``random.random()`` twice."""
+
+    def __init__(self, prob=0.15, factor=(0.75, 1.25)):
+        self.prob = _check_prob(prob)
+        self.factor = _check_range(factor, "factor")
+
+    def get_params(self):
+        coin, u = random.random(), random.random()
+        return coin < self.prob, float(np.float32(_value(self.factor, u)))
+
+    def __call__(self, img, label=None):
+        fire, factor = self.get_params()
+        if fire:
+            if _on_device(img):
+                from ..preprocess import INTENSITY_SCALE, intensity_apply_device
+                intensity_apply_device(img, INTENSITY_SCALE, [factor])
+            else:
+                img = np.asarray(img, np.float32) * np.float32(factor)
+        return img, label
+
+
+@manager.TRANSFORMS.add_component
+class RandomContrast3D:
+    """With probability ``prob``: (image - mean) * factor + mean, clamped to the image's own [min, max] with
+    ``preserve_range`` (batchgenerators' ContrastAugmentationTransform: a second coin picks the part of ``factor`` below or
+    above 1).  The mean is msk_intensity_stats' ordered float64 sum / n on both paths.  The label passes through.  Not in the
+    reference.  Random stream, whatever the coin: ``random.random()`` three times (coin, branch, value)."""
+
+    def __init__(self, prob=0.15, factor=(0.75, 1.25), preserve_range=True):
+        self.prob = _check_prob(prob)
+        self.factor = _check_range(factor, "factor", lowest=0.0)
+        self.preserve_range = bool(preserve_range)
+
+    def get_params(self):
+        coin, branch, u = random.random(), random.random(), random.random()
+        return coin < self.prob, float(np.float32(_branch_value(self.factor, branch, u)))
+
+    def __call__(self, img, label=None):
+        fire, factor = self.get_params()
+        if fire:
+            if _on_device(img):
+                from ..preprocess import INTENSITY_CONTRAST, intensity_apply_device, intensity_stats_device
+                rec = intensity_stats_device(img)
+                intensity_apply_device(img, INTENSITY_CONTRAST, [factor, float(self.preserve_range)], stats_a=rec)
+                rec.free()
+            else:
+                img = _contrast_host(img, factor, self.preserve_range)
+        return img, label
+
+
+@manager.TRANSFORMS.add_component
+class RandomGamma3D:
+    """With probability ``prob``: batchgenerators' augment_gamma -- the image (negated first with ``invert``) is scaled to
+    [0, 1] by its own range, raised to gamma (drawn like RandomContrast3D's factor), scaled back (and negated back); with
+    ``retain_stats`` the result is then shifted and scaled to the mean and standard deviation the image had before.  The
+    label passes through.  Not in the reference.  Random stream, whatever the coin: ``random.random()`` three times."""
+
+    def __init__(self, prob=0.3, gamma=(0.7, 1.5), invert=False, retain_stats=True):
+        self.prob = _check_prob(prob)
+        self.gamma = _check_range(gamma, "gamma", lowest=0.0)
+        if self.gamma[0] <= 0.0:
+            raise ValueError("gamma must be positive, got {}.".format(gamma))
+        self.invert = bool(invert)
+        self.retain_stats = bool(retain_stats)
+
+    def get_params(self):
+        coin, branch, u = random.random(), random.random(), random.random()
+        return coin < self.prob, float(np.float32(_branch_value(self.gamma, branch, u)))
+
+    def __call__(self, img, label=None):
+        fire, gamma = self.get_params()
+        if fire:
+            if _on_device(img):
+                from ..preprocess import INTENSITY_GAMMA, INTENSITY_RESTORE, intensity_apply_device, intensity_stats_device
+                before = intensity_stats_device(img)
+                intensity_apply_device(img, INTENSITY_GAMMA, [gamma, float(self.invert)], stats_a=before)
+                if self.retain_stats:
+                    after = intensity_stats_device(img)
+                    intensity_apply_device(img, INTENSITY_RESTORE, [], stats_a=before, stats_b=after)
+                    after.free()
+                before.free()
+            else:
+                img = np.asarray(img, np.float32)
+                before = _stats_host(img)
+                img = _gamma_host(img, gamma, self.invert, before)
+                if self.retain_stats:
+                    img = _restore_host(img, before, _stats_host(img))
+        return img, label
+
+
 def _connected_components(binary_mask, minimum_volume=0):
     """functional.py:117-131 (SimpleITK ConnectedComponent + RelabelComponent): face-connected
     components relabelled 1, 2, ... by decreasing size, components smaller than
