@@ -127,6 +127,7 @@ int msk_prof_report(msk_ctx* ctx, char* buf, int buflen, int* len);
  *   "bwd_fuse" -1|0|1|2 (msk_conv3d_bwd_bnact: auto | three calls | one dual transform | one transform per stream),
  *     "foldn_wgs" (workgroups per CU targeted by the D segmentation of conv_foldn_k, 0 = 2);
  *     "tk_join" 1|0 (msk_conv3d_bwd_bnact_join: 1 = the join backward runs in the data-gradient kernel's epilogue, 0 = it declines);
+ *     "affine_map" 1|0 (msk_affine_patch: 1 = a wavefront covers a 2 x 2 x 16 box of the patch, 0 = row-linear; same results);
  *     "wbf_pad_min_voxels" (smallest 5^3 problem whose channel counts are not multiples of 32 that is run through the
  *         16-bit pipeline on a zero-padded copy, default 2^18);
  *     "wbf_tin_groups" (workgroups below which the pipeline's transform kernels cut their W tiles into chunks, -1 = 8 per CU, 0 = never);
@@ -498,6 +499,26 @@ int msk_patch_select(msk_ctx* ctx, const int32_t* label, int d, int h, int w, in
  * or outside [0, num_classes), n_patches outside 1..16, dst overlapping src.                                                */
 int msk_patch_crop(msk_ctx* ctx, const void* src, int d, int h, int w, const int32_t* sel, void* dst, int rd, int rh, int rw,
                    uint32_t pad_bits);
+
+/* ---- rotated and scaled patch cropping (transforms.RandomAffinePatchCrop3D) ---- */
+/* out_img [rd,rh,rw] (and out_label) = the patch of img [d,h,w] float32 (and label, int32) whose sampling grid is built around
+ * the centre of ONE sel record of msk_patch_select (DEVICE; its first three words d0, h0, w0 are read on the device), turned
+ * and scaled by matrix (HOST, 9 floats, row-major: source axis x patch axis; read before the call returns), as
+ * tests/affine_reference.py states it.  For the output voxel (z, y, x), o = (z - rd/2, y - rh/2, x - rw/2), per source axis a:
+ *     p_a = ((M[a][0]*o_z + M[a][1]*o_y) + M[a][2]*o_x) + (float)(origin_a + roi_a/2)
+ * image: f = floor(p), t = p - f, the eight corners f + {0,1}^3 -- a corner outside the volume has the value pad and is not
+ * loaded (scipy's mode='grid-constant') -- and lerp(a, b, t) = a + t*(b - a) along w, then h, then d; label: the voxel at
+ * floor(p + 0.5f), label_pad outside the volume.  Every float operation is rounded on its own (no FMA), so the result equals
+ * the numpy statement bit for bit; with the identity matrix it equals msk_patch_crop (for data without negative zeros).
+ * label and out_label are both null or both set; image and label share the coordinates.  One launch on the context stream, a
+ * thread per output voxel (option "affine_map"), no atomics, no synchronisation, no download; nothing data-dependent can fail.
+ * Argument errors, reported before any launch: null img, sel, matrix or out_img; only one of label and out_label set;
+ * misaligned pointers (4 bytes); extents < 1 or > 8192 per axis (volume or patch); 2^31 voxels or more (volume or patch); a
+ * matrix entry that is not finite or whose magnitude exceeds 4 (with the extent limit this bounds |p| below 2^17, so every
+ * float -> int conversion is defined); outputs overlapping img, label, sel or each other.                                   */
+int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
+                     const float* matrix, float* out_img, int32_t* out_label, int rd, int rh, int rw, float pad,
+                     int32_t label_pad);
 
 /* ---- intensity augmentation (transforms.RandomGaussianNoise3D / RandomGaussianBlur3D / RandomBrightness3D /
  *      RandomContrast3D / RandomGamma3D; no reference call site: the reference has geometric augmentation only) ---- */

@@ -137,6 +137,7 @@ SIGNATURES = {
     "msk_patch_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),
     "msk_patch_select": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "msk_patch_crop": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _u32]),
+    "msk_affine_patch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_int32]),
     "msk_intensity_stats_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
     "msk_intensity_stats": (_i, [_vp, _vp, C.c_long, _vp, _vp]),
     "msk_intensity_apply": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp, _vp, _u64]),

@@ -619,6 +619,10 @@ int msk_set_option(msk_ctx* ctx, const char* key, int value) {
     ctx->tk_join = value != 0;
     return 0;
   }
+  if (strcmp(key, "affine_map") == 0) {  // msk_affine_patch: 1 = a compact box per wavefront, 0 = row-linear (A/B)
+    ctx->affine_map = value != 0;
+    return 0;
+  }
   if (strcmp(key, "foldn_wgs") == 0) {
     ctx->foldn_wgs = value > 0 ? value : 0;
     return 0;

@@ -188,6 +188,35 @@ def patch_crop_device(vol: DeviceVolume, sel: DeviceVolume, roi, pad=0, index=0)
     return out
 
 
+def affine_patch_device(img: DeviceVolume, label, sel: DeviceVolume, roi, matrix, pad=0, label_pad=0, index=0):
+    """msk_affine_patch: the patch of ``img`` (float32) and, unless ``label`` is None, of ``label`` (int32) whose sampling grid
+    is centred on the patch of record ``index`` of ``sel`` (patch_select_device; read on the device) and turned and scaled by
+    the 3x3 ``matrix`` (rows: source axes, columns: patch axes) -> one pooled ``DeviceVolume`` of extent ``roi``, or two.  The
+    image is read trilinearly with ``pad`` outside the volume, the label by nearest neighbour with ``label_pad``, from the
+    same coordinates, in one launch.  Nothing is downloaded and nothing synchronises."""
+    _float_volume(img, "affine_patch_device")
+    if label is not None and (not isinstance(label, DeviceVolume) or label.dtype != np.int32 or label.shape != img.shape):
+        raise TypeError("affine_patch_device takes an int32 DeviceVolume of the image's shape as the label")
+    if not 0 <= int(index) < sel.shape[0]:
+        raise ValueError("affine_patch_device: record {} of {}".format(index, sel.shape[0]))
+    m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float32).reshape(9))
+    out = _pooled_volume(img.dev, roi, np.float32)
+    out_label = None
+    try:
+        if label is not None:
+            out_label = _pooled_volume(img.dev, roi, np.int32)
+        img.dev.call("msk_affine_patch", C.c_void_p(img.ptr), C.c_void_p(label.ptr) if label is not None else None, *img.shape,
+                     C.c_void_p(sel.ptr + 32 * int(index)), m.ctypes.data_as(C.c_void_p), C.c_void_p(out.ptr),
+                     C.c_void_p(out_label.ptr) if label is not None else None, int(roi[0]), int(roi[1]), int(roi[2]),
+                     C.c_float(float(pad)), int(label_pad))
+    except MskError:
+        out.free()
+        if out_label is not None:
+            out_label.free()
+        raise
+    return out if label is None else (out, out_label)
+
+
 INTENSITY_NOISE, INTENSITY_SCALE, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_RESTORE = range(5)   # MSK_INTENSITY_*
 GAUSS_MAX_SIGMA = 2.0   # radius int(4 sigma + 0.5) <= 8, the widest msk_gauss_blur3d takes
 

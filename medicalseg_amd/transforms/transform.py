@@ -679,6 +679,128 @@ def _cc_device(x, minimum_volume=0, k=0):
     return _swap(x, out) if _on_device(x) else out
 
 
+# ---- rotated and scaled patch crop (nnU-Net's spatial augmentation without the elastic part; not in the reference) ---------
+def _affine_matrix(angles_deg, scales):
+    """M = Rd . Rh . Rw . diag(scales): right-handed rotations about the D, H and W axes, angles in degrees, computed in
+    float64 and rounded to float32 once (tests/affine_reference.py).  Rows are source axes, columns patch axes."""
+    import math
+    c = [math.cos(math.radians(float(a))) for a in angles_deg]
+    s = [math.sin(math.radians(float(a))) for a in angles_deg]
+    rd = np.array([[1.0, 0.0, 0.0], [0.0, c[0], -s[0]], [0.0, s[0], c[0]]], np.float64)
+    rh = np.array([[c[1], 0.0, s[1]], [0.0, 1.0, 0.0], [-s[1], 0.0, c[1]]], np.float64)
+    rw = np.array([[c[2], -s[2], 0.0], [s[2], c[2], 0.0], [0.0, 0.0, 1.0]], np.float64)
+    return (rd @ rh @ rw @ np.diag(np.asarray(scales, np.float64))).astype(np.float32)
+
+
+def _affine_gather(vol, idx, outside):
+    ok = np.ones(idx[0].shape, bool)
+    clipped = []
+    for i, n in zip(idx, vol.shape):
+        ok &= (i >= 0) & (i < n)
+        clipped.append(np.clip(i, 0, n - 1))
+    return np.where(ok, vol[tuple(clipped)], outside)
+
+
+def _affine_patch_host(img, label, origin, roi, m, pad, label_pad):
+    """msk_affine_patch in numpy, float32 throughout, every operation rounded on its own: the grid of the patch, centred on
+    origin + roi // 2, through the matrix; the image trilinearly (W, then H, then D; ``pad`` outside the volume), the label
+    at floor(p + 0.5) (``label_pad`` outside).  Equal to tests/affine_reference.py bit for bit."""
+    img = np.asarray(img, np.float32)
+    m = np.asarray(m, np.float32).reshape(3, 3)
+    oz, oy, ox = ((np.arange(r) - r // 2).astype(np.float32).reshape(sh)
+                  for r, sh in zip(roi, ((-1, 1, 1), (1, -1, 1), (1, 1, -1))))
+    p = [((m[a, 0] * oz + m[a, 1] * oy) + m[a, 2] * ox) + np.float32(int(origin[a]) + int(roi[a]) // 2) for a in range(3)]
+    f = [np.floor(v) for v in p]
+    t = [v - fl for v, fl in zip(p, f)]
+    i0 = [fl.astype(np.int64) for fl in f]
+    pad = np.float32(pad)
+
+    def lerp(a, b, w):
+        return a + w * (b - a)
+
+    def along_w(dz, dy):
+        return lerp(_affine_gather(img, (i0[0] + dz, i0[1] + dy, i0[2]), pad),
+                    _affine_gather(img, (i0[0] + dz, i0[1] + dy, i0[2] + 1), pad), t[2])
+    out = lerp(lerp(along_w(0, 0), along_w(0, 1), t[1]), lerp(along_w(1, 0), along_w(1, 1), t[1]), t[0])
+    if label is None:
+        return out, None
+    near = [np.floor(v + np.float32(0.5)).astype(np.int64) for v in p]
+    return out, _affine_gather(np.asarray(label), near, np.asarray(label).dtype.type(label_pad))
+
+
+@manager.TRANSFORMS.add_component
+class RandomAffinePatchCrop3D(RandomPatchCrop3D):
+    """RandomPatchCrop3D whose patch is, with probability ``rotate_prob``, rotated about all three axes and, with
+    probability ``scale_prob``, zoomed -- nnU-Net's spatial augmentation: the sampling grid of the patch is built around the
+    chosen centre, turned and scaled, and the volume is read once (the image trilinearly, the label by nearest neighbour from
+    the same coordinates), so the cost follows the patch and there is one interpolation.  Not in the reference.
+
+    ``degrees``: a number d (every axis in [-d, d]), a (low, high) pair for every axis, or three pairs for the rotations
+    about D, H and W -- ``[[-15, 15], [0, 0], [0, 0]]`` turns a thin slab in-plane only.  ``scale``: a range inside
+    [0.25, 4]; a value above 1 reads a larger region, so the content shrinks; a second coin picks the part of the range below
+    or above 1 (nnU-Net's rule), and ``per_axis_scale`` draws one value per axis instead of one for all.
+
+    Random stream: the parent's six draws, then always nine ``random.random()``: the rotate coin, three angles, the scale
+    coin, the branch coin, three scales (without ``per_axis_scale`` only the first is used).  When neither coin hits the
+    patch is the parent's: the same select and the same plain crops, and msk_affine_patch is not launched.  On device volumes msk_patch_select and msk_affine_patch run back to back:
+    the origin never visits the host and nothing synchronises."""
+
+    def __init__(self, size, num_classes, fg_prob=1. / 3., classes=None, pad_value=0, label_pad=0, rotate_prob=0.2, degrees=30,
+                 scale_prob=0.2, scale=(0.7, 1.4), per_axis_scale=False):
+        super().__init__(size, num_classes, fg_prob, classes, pad_value, label_pad)
+        self.rotate_prob = _check_prob(rotate_prob)
+        self.scale_prob = _check_prob(scale_prob)
+        if isinstance(degrees, numbers.Number):
+            if degrees < 0:
+                raise ValueError("If degrees is a single number, it must be positive.")
+            degrees = (-degrees, degrees)
+        if isinstance(degrees, (tuple, list)) and len(degrees) == 3 and all(isinstance(d, (tuple, list)) for d in degrees):
+            per_axis = list(degrees)
+        else:
+            per_axis = [degrees] * 3
+        try:
+            self.degrees = [_check_range(d, "degrees", lowest=-180.0, highest=180.0) for d in per_axis]
+        except TypeError:
+            raise ValueError("degrees must be a number, a (low, high) pair or three pairs, got {}.".format(degrees))
+        self.scale = _check_range(scale, "scale", lowest=0.25, highest=4.0)
+        self.per_axis_scale = bool(per_axis_scale)
+
+    def get_matrix(self):
+        """the nine draws -> the float32 matrix, or None when neither coin hit"""
+        u = [random.random() for _ in range(9)]
+        rotate, scale = u[0] < self.rotate_prob, u[4] < self.scale_prob
+        if not rotate and not scale:
+            return None
+        angles = [_value(rng, v) for rng, v in zip(self.degrees, u[1:4])] if rotate else [0.0, 0.0, 0.0]
+        su = u[6:9] if self.per_axis_scale else [u[6]] * 3
+        scales = [_branch_value(self.scale, u[5], v) for v in su] if scale else [1.0, 1.0, 1.0]
+        return _affine_matrix(angles, scales)
+
+    def __call__(self, img, label=None):
+        words = self.get_params(label is not None)
+        m = self.get_matrix()
+        if _on_device(img):
+            from ..preprocess import affine_patch_device, patch_crop_device, patch_select_device
+            sel = patch_select_device(img if label is None else label, self.size, self.num_classes,
+                                      [] if label is None else self.classes, words)
+            try:
+                if m is None:                # neither coin hit: the parent's two crops, msk_affine_patch is not launched
+                    out = patch_crop_device(img, sel, self.size, self.pad_value)
+                    out_label = None if label is None else patch_crop_device(label, sel, self.size, self.label_pad)
+                elif label is None:
+                    out, out_label = affine_patch_device(img, None, sel, self.size, m, self.pad_value), None
+                else:
+                    out, out_label = affine_patch_device(img, label, sel, self.size, m, self.pad_value, self.label_pad)
+            finally:
+                sel.free()
+            return _swap(img, out), None if label is None else _swap(label, out_label)
+        origin = self.select(img.shape[:3], label, words)[:3]
+        if m is None:
+            return (_patch_crop_host(img, origin, self.size, self.pad_value),
+                    None if label is None else _patch_crop_host(label, origin, self.size, self.label_pad))
+        return _affine_patch_host(img, label, origin, self.size, m, self.pad_value, self.label_pad)
+
+
 @manager.TRANSFORMS.add_component
 class BinaryMaskToConnectComponent:
     """numpy masks: the scipy path, uint32 labels.  A ``DeviceVolume`` or an ``IntTensor`` [N, 1, D, H, W] (the
