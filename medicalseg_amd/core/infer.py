@@ -45,18 +45,67 @@ def inference(model, im, ori_shape=None, transforms=None):
     An eval-mode model runs its conv -> BN -> PReLU units as single folded convolutions here
     (nn.fused_inference); a model left in training mode runs the ordinary kernels."""
     with nn.fused_inference():
-        logits = model(im)
+        logit = _forward(model, im)
+    return _finish(logit, ori_shape, transforms)
+
+
+# ---- what the three prediction paths (inference, aug_inference, sliding_window_inference) share ------------------------------
+def _forward(model, x):
+    """model(x)[0], the full-resolution logits"""
+    logits = model(x)
     if not isinstance(logits, collections.abc.Sequence):
         raise TypeError("The type of logits must be one of collections.abc.Sequence, e.g. list, tuple. "
                         "But received {}".format(type(logits)))
-    logit = logits[0]
+    return logits[0]
+
+
+def _new_pred(logit):
+    """an int32 [N,1,D,H,W] prediction for `logit` in the activation arena, not yet written"""
+    dev = logit.dev
+    return IntTensor(dev, dev.arena.alloc(logit.voxels * 4), (logit.n, 1, logit.d, logit.h, logit.w), dev.arena.gen)
+
+
+def _finish(logit, ori_shape, transforms):
+    """-> (pred, logit): the logits (or probabilities) resized back when `ori_shape` differs from their extent, then their
+    argmax"""
     if ori_shape is not None and tuple(ori_shape) != tuple(logit.shape[2:]):
         logit = reverse_transform(logit, ori_shape, transforms, mode='bilinear')
-    dev = logit.dev
-    ptr = dev.arena.alloc(logit.voxels * 4)
-    dev.call("msk_argmax_c", logit.msk(), C.c_void_p(ptr))
-    pred = IntTensor(dev, ptr, (logit.n, 1, logit.d, logit.h, logit.w), dev.arena.gen)
+    pred = _new_pred(logit)
+    logit.dev.call("msk_argmax_c", logit.msk(), C.c_void_p(pred.ptr))
     return pred, logit
+
+
+def _kept(dev, key, n, d, h, w, c):
+    """The persistent device tensor under `key` in dev.kept, outside the activation arena (every model forward resets the
+    arena): allocated on first use, reused while the shape asked for is the one kept, freed and replaced when it is not.  A
+    key that contains the shape therefore keeps one buffer per shape, a key without it one buffer."""
+    shape = (int(n), int(d), int(h), int(w), int(c))
+    t = dev.kept.get(key)
+    if t is not None and (t.n, t.d, t.h, t.w, t.c) != shape:
+        dev.free(dev.kept.pop(key).ptr)
+        t = None
+    if t is None:
+        t = dev.kept[key] = Tensor.empty(dev, *shape, arena=False)
+    return t
+
+
+def _release(dev, family):
+    """free what dev.kept holds under the keys (family, ...), in the order it was allocated, and nothing else"""
+    for key in [k for k in dev.kept if k[0] == family]:
+        v = dev.kept.pop(key)
+        for p in (v[1] if isinstance(v, tuple) else [v.ptr]):      # (plan, table pointers), or a Tensor
+            dev.free(p)
+
+
+def _copy_into(kept, t):
+    """`t` copied into the kept buffer of its shape (msk_flip_axes mirroring no axis) -> kept"""
+    t.dev.call("msk_flip_axes", t.msk(), kept.msk(), 0)
+    return kept
+
+
+def _restamp(kept):
+    """A kept buffer stamped like an activation of the last forward: stale after the next one, a new object per call."""
+    return Tensor(kept.dev, kept.ptr, kept.n, kept.d, kept.h, kept.w, kept.c, kept.c, kept.dev.arena.gen)
 
 
 # ----------------------------------------------------------------------------------------
@@ -95,18 +144,12 @@ def _tta_buffer(dev, role, n, d, h, w, c):
     """A persistent device tensor per (role, shape), outside the activation arena: every model forward resets the arena, and
     the accumulator, the kept plain logits and the mirrored / resized inputs have to outlive one.  After the first
     aug_inference at a shape no call allocates device memory; tta_release frees the buffers."""
-    cache = dev.__dict__.setdefault("_tta_buffers", {})
-    key = (role, int(n), int(d), int(h), int(w), int(c))
-    t = cache.get(key)
-    if t is None:
-        t = cache[key] = Tensor.empty(dev, n, d, h, w, c, arena=False)
-    return t
+    return _kept(dev, ("tta", role, int(n), int(d), int(h), int(w), int(c)), n, d, h, w, c)
 
 
 def tta_release(dev):
     """Free the persistent buffers of aug_inference on `dev` (they are kept per shape, for the device's lifetime otherwise)."""
-    for t in dev.__dict__.pop("_tta_buffers", {}).values():
-        dev.free(t.ptr)
+    _release(dev, "tta")
 
 
 def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_axes=(), with_plain=False):
@@ -141,11 +184,7 @@ def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_a
                 xf = _tta_buffer(dev, "mirrored", x.n, x.d, x.h, x.w, x.c)
                 dev.call("msk_flip_axes", x.msk(), xf.msk(), mask)
                 x = xf
-            logits = model(x)
-            if not isinstance(logits, collections.abc.Sequence):
-                raise TypeError("The type of logits must be one of collections.abc.Sequence, e.g. list, tuple. "
-                                "But received {}".format(type(logits)))
-            logit = logits[0]
+            logit = _forward(model, x)
             if scale != 1.0:
                 back = Tensor.empty(dev, logit.n, extent[0], extent[1], extent[2], logit.c)
                 dev.call("msk_interp_trilinear_fwd", logit.msk(), back.msk())
@@ -153,22 +192,17 @@ def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_a
             if acc is None:
                 acc = _tta_buffer(dev, "acc", logit.n, logit.d, logit.h, logit.w, logit.c)
             if with_plain and plain is None and scale == 1.0 and mask == 0:
-                plain = _tta_buffer(dev, "plain", logit.n, logit.d, logit.h, logit.w, logit.c)
-                dev.call("msk_flip_axes", logit.msk(), plain.msk(), 0)
+                plain = _copy_into(_tta_buffer(dev, "plain", logit.n, logit.d, logit.h, logit.w, logit.c), logit)
             dev.call("msk_tta_accumulate", logit.msk(), mask, acc.msk(), 1 if k == 0 else 0)
-    if plain is not None:      # stamped like an activation of the last forward: stale after the next one, a new object per call
-        plain = Tensor(dev, plain.ptr, plain.n, plain.d, plain.h, plain.w, plain.c, plain.c, dev.arena.gen)
+    if plain is not None:
+        plain = _restamp(plain)
     probs = Tensor.empty(dev, acc.n, acc.d, acc.h, acc.w, acc.c)
-    resize = ori_shape is not None and tuple(ori_shape) != tuple(probs.shape[2:])
-    if resize:
+    if ori_shape is not None and tuple(ori_shape) != tuple(probs.shape[2:]):
         dev.call("msk_tta_finish", acc.msk(), len(passes), probs.msk(), None)
-        probs = reverse_transform(probs, ori_shape, transforms, mode='bilinear')
-    ptr = dev.arena.alloc(probs.voxels * 4)
-    if resize:
-        dev.call("msk_argmax_c", probs.msk(), C.c_void_p(ptr))
-    else:
-        dev.call("msk_tta_finish", acc.msk(), len(passes), probs.msk(), C.c_void_p(ptr))
-    pred = IntTensor(dev, ptr, (probs.n, 1, probs.d, probs.h, probs.w), dev.arena.gen)
+        pred, probs = _finish(probs, ori_shape, transforms)
+    else:                      # nothing to resize: the mean and its argmax in one pass
+        pred = _new_pred(probs)
+        dev.call("msk_tta_finish", acc.msk(), len(passes), probs.msk(), C.c_void_p(pred.ptr))
     return (pred, probs, plain) if with_plain else (pred, probs)
 
 
@@ -263,31 +297,18 @@ class SlidingPlan:
         return (b, self.starts[0][i] - self.before[0], self.starts[1][j] - self.before[1], self.starts[2][k] - self.before[2])
 
 
-def _sw_cache(dev):
-    return dev.__dict__.setdefault("_sw_buffers", {})
-
-
 def _sw_buffer(dev, role, n, d, h, w, c):
     """The persistent device tensor of a role (the patch batch, the accumulator, the kept input) outside the activation arena:
     they have to outlive the forwards.  One per role: a call at the same shape reuses it and allocates nothing, a call at
     another shape frees it first -- native-resolution volumes differ in extent, and a whole-volume accumulator per distinct
     extent (0.9 GB at 300 x 512 x 512, C = 3) would otherwise stay for the device's lifetime.  sliding_release frees them."""
-    cache = _sw_cache(dev)
-    shape = (int(n), int(d), int(h), int(w), int(c))
-    t = cache.get((role,))
-    if t is not None and (t.n, t.d, t.h, t.w, t.c) != shape:
-        dev.free(cache.pop((role,)).ptr)
-        t = None
-    if t is None:
-        t = cache[(role,)] = Tensor.empty(dev, *shape, arena=False)
-    return t
+    return _kept(dev, ("sw", role), n, d, h, w, c)
 
 
 def _sw_plan(dev, shape, roi_size, overlap, mode, sigma_scale):
     """-> (SlidingPlan, [td, th, tw] device pointers): the plan of a geometry and its three tables, uploaded once"""
-    cache = _sw_cache(dev)
-    key = ("plan", tuple(int(v) for v in shape), tuple(roi_size), float(overlap), mode, float(sigma_scale))
-    hit = cache.get(key)
+    key = ("sw", "plan", tuple(int(v) for v in shape), tuple(roi_size), float(overlap), mode, float(sigma_scale))
+    hit = dev.kept.get(key)
     if hit is None:
         plan = SlidingPlan(shape, roi_size, overlap, mode, sigma_scale)
         ptrs = []
@@ -295,7 +316,7 @@ def _sw_plan(dev, shape, roi_size, overlap, mode, sigma_scale):
             p = dev.malloc(T.nbytes)
             dev.h2d(p, T)
             ptrs.append(p)
-        hit = cache[key] = (plan, ptrs)
+        hit = dev.kept[key] = (plan, ptrs)
     return hit
 
 
@@ -304,12 +325,7 @@ def sliding_release(dev):
     _sw_buffer); the plans with their three small device tables are kept per geometry, for the device's lifetime otherwise.
     The `logits` an earlier call returned IS the accumulator freed here: it must not be used after a release (its liveness
     check cannot know; until the next forward it still passes)."""
-    for key, v in dev.__dict__.pop("_sw_buffers", {}).items():
-        if key[0] == "plan":
-            for p in v[1]:
-                dev.free(p)
-        else:
-            dev.free(v.ptr)
+    _release(dev, "sw")
 
 
 def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', sigma_scale=0.125, sw_batch_size=1, cval=0.0,
@@ -338,9 +354,7 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
     plan, (td, th, tw) = _sw_plan(dev, (im.d, im.h, im.w), roi_size, overlap, mode, sigma_scale)
     rd, rh, rw = plan.roi_size
     if im.gen is not None:          # an activation: the first forward would reset the arena under it
-        kept = _sw_buffer(dev, "im", im.n, im.d, im.h, im.w, im.c)
-        dev.call("msk_flip_axes", im.msk(), kept.msk(), 0)
-        im = kept
+        im = _copy_into(_sw_buffer(dev, "im", im.n, im.d, im.h, im.w, im.c), im)
     windows = plan.windows(im.n)
     batch = min(int(sw_batch_size), len(windows))
     patches = _sw_buffer(dev, "patches", batch, rd, rh, rw, im.c)
@@ -353,11 +367,7 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
             corners = np.ascontiguousarray(origins[:, :4])
             x = patches if len(group) == batch else Tensor(dev, patches.ptr, len(group), rd, rh, rw, im.c)
             dev.call("msk_sw_gather", im.msk(), x.msk(), corners.ctypes.data_as(C.c_void_p), C.c_float(cval))
-            logits = model(x)
-            if not isinstance(logits, collections.abc.Sequence):
-                raise TypeError("The type of logits must be one of collections.abc.Sequence, e.g. list, tuple. "
-                                "But received {}".format(type(logits)))
-            logit = logits[0]
+            logit = _forward(model, x)
             if (logit.n, logit.d, logit.h, logit.w) != (len(group), rd, rh, rw):
                 raise ValueError("sliding_window_inference: the model maps a window batch of extent %r to %r; the logits "
                                  "must keep the window's extent" % ((len(group), rd, rh, rw), (logit.n, logit.d, logit.h, logit.w)))
@@ -366,11 +376,4 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
                 dev.memset(acc.ptr, 0, acc.voxels * acc.c * 4)
             dev.call("msk_sw_accumulate", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
                      C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], acc.msk())
-    # stamped like an activation of the last forward: stale after the next one, a new object per call
-    logit = Tensor(dev, acc.ptr, acc.n, acc.d, acc.h, acc.w, acc.c, acc.c, dev.arena.gen)
-    if ori_shape is not None and tuple(ori_shape) != tuple(logit.shape[2:]):
-        logit = reverse_transform(logit, ori_shape, transforms, mode='bilinear')
-    ptr = dev.arena.alloc(logit.voxels * 4)
-    dev.call("msk_argmax_c", logit.msk(), C.c_void_p(ptr))
-    pred = IntTensor(dev, ptr, (logit.n, 1, logit.d, logit.h, logit.w), dev.arena.gen)
-    return pred, logit
+    return _finish(_restamp(acc), ori_shape, transforms)

@@ -9,7 +9,6 @@ import numpy as np
 from .. import nn
 from ..datasets import DataLoader
 from ..device import to_tensor
-from ..device import Tensor
 from ..utils import TimeAverager, logger, loss_computation, metric, save_array
 from . import infer
 
@@ -86,6 +85,24 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                          % (scales,))
     if sliding_window is not None and aug_eval:
         raise ValueError("evaluate: sliding_window together with aug_eval=True is not supported")
+
+    # the chosen prediction path as one callable -> (pred, logits, mean_probs or None)
+    if aug_eval:
+        def predict(im, ori_shape):
+            transforms = eval_dataset.transforms.transforms
+            pred, mean_probs, logits = infer.aug_inference(model, im, ori_shape=ori_shape, transforms=transforms, scales=scales,
+                                                           flip_axes=flip_axes, with_plain=True)
+            if tuple(ori_shape) != tuple(logits.shape[2:]):      # as inference() does before the loss
+                logits = infer.reverse_transform(logits, ori_shape, transforms, mode='bilinear')
+            return pred, logits, mean_probs
+    elif sliding_window is not None:
+        def predict(im, ori_shape):
+            return infer.sliding_window_inference(model, im, sliding_window, overlap=sw_overlap, mode=sw_mode,
+                                                  sw_batch_size=sw_batch_size, ori_shape=ori_shape,
+                                                  transforms=eval_dataset.transforms.transforms) + (None,)
+    else:
+        def predict(im, ori_shape):
+            return infer.inference(model, im, ori_shape=ori_shape, transforms=eval_dataset.transforms.transforms) + (None,)
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -113,21 +130,7 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         for it, (im, label, idx) in enumerate(loader):
             reader_cost_averager.record(time.time() - batch_start)
             label_t = to_tensor(label.astype('int32'))
-            if aug_eval:
-                pred, mean_probs, logits = infer.aug_inference(model, to_tensor(im), ori_shape=label.shape[-3:],
-                                                               transforms=eval_dataset.transforms.transforms,
-                                                               scales=scales, flip_axes=flip_axes, with_plain=True)
-                if tuple(label.shape[-3:]) != tuple(logits.shape[2:]):      # as inference() does before the loss
-                    logits = infer.reverse_transform(logits, label.shape[-3:], eval_dataset.transforms.transforms,
-                                                     mode='bilinear')
-            elif sliding_window is not None:
-                pred, logits = infer.sliding_window_inference(model, to_tensor(im), sliding_window, overlap=sw_overlap,
-                                                              mode=sw_mode, sw_batch_size=sw_batch_size,
-                                                              ori_shape=label.shape[-3:],
-                                                              transforms=eval_dataset.transforms.transforms)
-            else:
-                pred, logits = infer.inference(model, to_tensor(im), ori_shape=label.shape[-3:],
-                                               transforms=eval_dataset.transforms.transforms)
+            pred, logits, mean_probs = predict(to_tensor(im), label.shape[-3:])
             loss, per_channel_dice = loss_computation(logits, label_t, new_loss)
             loss = sum(loss)
             if hard_metrics or surface_metrics:
@@ -141,15 +144,13 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
             if surface_metrics:
                 surface_cases.append(metric.surface_metrics(hard, label_t, num_classes, spacing=surface_spacing))
             if auc_roc:
-                lg = logits[0] if isinstance(logits, (list, tuple)) else logits
-                if aug_eval:
-                    probs = mean_probs                                        # the mean softmax over the passes
-                else:
-                    probs = Tensor.empty(lg.dev, lg.n, lg.d, lg.h, lg.w, lg.c)
-                    lg.dev.call("msk_softmax_c", lg.msk(), probs.msk())       # F.softmax(logits, axis=1) on the device
+                probs = mean_probs                                            # aug_eval: the mean softmax over the passes
+                if probs is None:
+                    probs = logits.empty_like()
+                    logits.dev.call("msk_softmax_c", logits.msk(), probs.msk())   # F.softmax(logits, axis=1) on the device
                 if auc_device:
                     if auc_scores is None:      # room for the whole set at the size of the first volume; grows otherwise
-                        auc_scores = metric.AucScores(lg.dev, num_classes, total_iters * probs.voxels)
+                        auc_scores = metric.AucScores(logits.dev, num_classes, total_iters * probs.voxels)
                     auc_scores.add(probs, label_t)
                 else:
                     logits_all.append(probs.numpy())

@@ -163,7 +163,7 @@ class DataLoader:
         if any(v.shape != shape for v in ims + labs):
             raise ValueError("device batching needs equal sample shapes, got {}".format([v.shape for v in ims]))
         n, vox = len(ims), int(np.prod(shape))
-        slots = DataLoader._slots.setdefault((id(dev), n, shape), {"bufs": [], "next": 0})
+        slots = DataLoader._slots.setdefault((dev, n, shape), {"bufs": [], "next": 0})
         if len(slots["bufs"]) < 2:
             slots["bufs"].append((dev.malloc(n * vox * 4), dev.malloc(n * vox * 4)))
             xb, yb = slots["bufs"][-1]

@@ -35,6 +35,9 @@ class Device:
         self.rank = 0
         self.world = 1
         self._small = []
+        # device memory that outlives one call belongs to the device object, so it cannot outlive it under a recycled id():
+        self.pool = {}     # stream-ordered free lists (preprocess._pool_alloc): size in bytes -> LIFO list of pointers
+        self.kept = {}     # persistent inference buffers (core.infer._kept): key -> Tensor, or (plan, table pointers)
 
     # -- low level -----------------------------------------------------------------
     def call(self, name, *args):

@@ -5,6 +5,7 @@ pinned-host -> device copies, processed by HIP kernels, and returned as host arr
 ``*_device`` variants keep data on the GPU for in-loop use."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -39,17 +40,14 @@ class DeviceVolume:
 
 # Stream-ordered recycling of augmentation buffers: every op is enqueued on the context's single
 # stream, so a buffer released by one op can be handed to a later op without synchronising
-# (hipFree would stall the loader on the whole training stream).
-_POOL = {}
-
-
+# (hipFree would stall the loader on the whole training stream).  The free lists are the device object's own (Device.pool).
 def _pool_alloc(dev, nbytes):
-    free = _POOL.setdefault(id(dev), {}).setdefault(int(nbytes), [])
+    free = dev.pool.get(int(nbytes))
     return free.pop() if free else dev.malloc(nbytes)
 
 
 def _pool_release(dev, ptr, nbytes):
-    _POOL.setdefault(id(dev), {}).setdefault(int(nbytes), []).append(ptr)
+    dev.pool.setdefault(int(nbytes), []).append(ptr)
 
 
 def _pooled_volume(dev, shape, dtype) -> DeviceVolume:
@@ -57,6 +55,51 @@ def _pooled_volume(dev, shape, dtype) -> DeviceVolume:
     v = DeviceVolume(dev, _pool_alloc(dev, int(np.prod(shape)) * np.dtype(dtype).itemsize), shape, dtype)
     v.pooled = True
     return v
+
+
+def _new_volume(dev, shape, dtype, pooled) -> DeviceVolume:
+    """a volume from the pool, or one of its own allocation (``free()`` is hipFree then, which synchronises)"""
+    if pooled:
+        return _pooled_volume(dev, shape, dtype)
+    shape = tuple(int(v) for v in shape)
+    return DeviceVolume(dev, dev.malloc(int(np.prod(shape)) * np.dtype(dtype).itemsize), shape, dtype)
+
+
+@contextlib.contextmanager
+def _pooled_outputs(dev, *specs):
+    """The output volumes of one device op, a (shape, dtype) each, taken from the pool in the order given (None: no such
+    output, yielded as None); a body that raises -- the library refused the call -- hands them back."""
+    outs = []
+    try:
+        for spec in specs:
+            outs.append(None if spec is None else _pooled_volume(dev, *spec))
+        yield outs
+    except BaseException:
+        for v in outs:
+            if v is not None:
+                v.free()
+        raise
+
+
+@contextlib.contextmanager
+def _pooled_scratch(dev, nbytes):
+    """Scratch of one device op from the pool, handed back whatever happens: every later op is enqueued behind this one on
+    the same stream.  ``nbytes`` None: the op needs none, yields None."""
+    ptr = None if nbytes is None else _pool_alloc(dev, nbytes)
+    try:
+        yield ptr
+    finally:
+        if ptr is not None:
+            _pool_release(dev, ptr, nbytes)
+
+
+def _workspace_bytes(dev, query, *args):
+    """the scratch size one of the library's msk_*_workspace queries (they take no context) asks for"""
+    nbytes = C.c_size_t(0)
+    if getattr(dev.lib, query)(*args, C.byref(nbytes)) != 0:
+        from ._lib import last_error
+        raise MskError(query + " failed: " + last_error(None))
+    return nbytes.value
 
 
 def _dt(vol):
@@ -122,13 +165,10 @@ def connected_components_device(x, minimum_volume=0, k=0):
     else:
         raise TypeError("connected_components_device takes a DeviceVolume or an IntTensor, got {}".format(type(x)))
     dev = x.dev
-    st = _pool_alloc(dev, 4 * n)
-    try:
+    with _pooled_scratch(dev, 4 * n) as st:
         dev.call("msk_connected_components3d", C.c_void_p(x.ptr), C.c_void_p(out_ptr), n, d, h, w, dtype, mv, k,
                  C.c_void_p(st), None)
         status = dev.d2h(st, (n,), np.int32)
-    finally:
-        _pool_release(dev, st, 4 * n)
     if status.any():
         if isinstance(out, DeviceVolume):
             out.free()
@@ -154,21 +194,11 @@ def patch_select_device(label: DeviceVolume, roi, num_classes, classes, words) -
     d, h, w = label.shape
     words = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).astype(np.uint32).reshape(-1, 6))
     cls = np.ascontiguousarray(np.asarray(list(classes), dtype=np.int32).reshape(-1))
-    nbytes = C.c_size_t(0)
-    if dev.lib.msk_patch_workspace(C.c_long(d * h * w), int(num_classes), C.byref(nbytes)) != 0:
-        from ._lib import last_error
-        raise MskError("msk_patch_workspace failed: " + last_error(None))
-    sel = _pooled_volume(dev, (len(words), 8), np.int32)
-    ws = _pool_alloc(dev, nbytes.value)
-    try:
+    nbytes = _workspace_bytes(dev, "msk_patch_workspace", C.c_long(d * h * w), int(num_classes))
+    with _pooled_outputs(dev, ((len(words), 8), np.int32)) as (sel,), _pooled_scratch(dev, nbytes) as ws:
         dev.call("msk_patch_select", C.c_void_p(label.ptr), d, h, w, int(num_classes), cls.ctypes.data_as(C.c_void_p), len(cls),
                  int(roi[0]), int(roi[1]), int(roi[2]), words.ctypes.data_as(C.c_void_p), len(words), C.c_void_p(ws),
                  C.c_void_p(sel.ptr), None)
-    except MskError:
-        sel.free()
-        raise
-    finally:
-        _pool_release(dev, ws, nbytes.value)
     return sel
 
 
@@ -177,14 +207,10 @@ def patch_crop_device(vol: DeviceVolume, sel: DeviceVolume, roi, pad=0, index=0)
     device -> a pooled ``DeviceVolume`` of extent ``roi`` and vol's dtype; voxels outside the volume are ``pad``."""
     if not 0 <= int(index) < sel.shape[0]:
         raise ValueError("patch_crop_device: record {} of {}".format(index, sel.shape[0]))
-    out = _pooled_volume(vol.dev, roi, vol.dtype)
-    bits = int(np.array([pad], dtype=vol.dtype).view(np.uint32)[0])
-    try:
+    with _pooled_outputs(vol.dev, (roi, vol.dtype)) as (out,):
+        bits = int(np.array([pad], dtype=vol.dtype).view(np.uint32)[0])
         vol.dev.call("msk_patch_crop", C.c_void_p(vol.ptr), *vol.shape, C.c_void_p(sel.ptr + 32 * int(index)), C.c_void_p(out.ptr),
                      int(roi[0]), int(roi[1]), int(roi[2]), C.c_uint32(bits))
-    except MskError:
-        out.free()
-        raise
     return out
 
 
@@ -200,20 +226,11 @@ def affine_patch_device(img: DeviceVolume, label, sel: DeviceVolume, roi, matrix
     if not 0 <= int(index) < sel.shape[0]:
         raise ValueError("affine_patch_device: record {} of {}".format(index, sel.shape[0]))
     m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float32).reshape(9))
-    out = _pooled_volume(img.dev, roi, np.float32)
-    out_label = None
-    try:
-        if label is not None:
-            out_label = _pooled_volume(img.dev, roi, np.int32)
+    with _pooled_outputs(img.dev, (roi, np.float32), None if label is None else (roi, np.int32)) as (out, out_label):
         img.dev.call("msk_affine_patch", C.c_void_p(img.ptr), C.c_void_p(label.ptr) if label is not None else None, *img.shape,
                      C.c_void_p(sel.ptr + 32 * int(index)), m.ctypes.data_as(C.c_void_p), C.c_void_p(out.ptr),
                      C.c_void_p(out_label.ptr) if label is not None else None, int(roi[0]), int(roi[1]), int(roi[2]),
                      C.c_float(float(pad)), int(label_pad))
-    except MskError:
-        out.free()
-        if out_label is not None:
-            out_label.free()
-        raise
     return out if label is None else (out, out_label)
 
 
@@ -248,19 +265,9 @@ def intensity_stats_device(vol: DeviceVolume) -> DeviceVolume:
     Nothing is downloaded and nothing synchronises: the record is read by msk_intensity_apply on the device."""
     _float_volume(vol, "intensity_stats_device")
     dev = vol.dev
-    nbytes = C.c_size_t(0)
-    if dev.lib.msk_intensity_stats_workspace(C.c_long(vol.size), C.byref(nbytes)) != 0:
-        from ._lib import last_error
-        raise MskError("msk_intensity_stats_workspace failed: " + last_error(None))
-    rec = _pooled_volume(dev, (4,), np.float64)
-    ws = _pool_alloc(dev, nbytes.value)
-    try:
+    nbytes = _workspace_bytes(dev, "msk_intensity_stats_workspace", C.c_long(vol.size))
+    with _pooled_outputs(dev, ((4,), np.float64)) as (rec,), _pooled_scratch(dev, nbytes) as ws:
         dev.call("msk_intensity_stats", C.c_void_p(vol.ptr), C.c_long(vol.size), C.c_void_p(ws), C.c_void_p(rec.ptr))
-    except MskError:
-        rec.free()
-        raise
-    finally:
-        _pool_release(dev, ws, nbytes.value)
     return rec
 
 
@@ -273,15 +280,11 @@ def intensity_apply_device(vol: DeviceVolume, mode, params, stats_a=None, stats_
     p = np.zeros(4, np.float32)
     params = np.asarray(params, np.float32).reshape(-1)
     p[:params.size] = params
-    out = vol if inplace else _pooled_volume(vol.dev, vol.shape, vol.dtype)
-    try:
+    with _pooled_outputs(vol.dev, None if inplace else (vol.shape, vol.dtype)) as (out,):
+        out = vol if inplace else out
         vol.dev.call("msk_intensity_apply", C.c_void_p(vol.ptr), C.c_void_p(out.ptr), C.c_long(vol.size), int(mode),
                      p.ctypes.data_as(C.c_void_p), C.c_void_p(stats_a.ptr) if stats_a is not None else None,
                      C.c_void_p(stats_b.ptr) if stats_b is not None else None, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF))
-    except MskError:
-        if out is not vol:
-            out.free()
-        raise
     return out
 
 
@@ -297,47 +300,34 @@ def gauss_blur_device(vol: DeviceVolume, sigma) -> DeviceVolume:
         raise ValueError("sigma must be a scalar or three values, got {}".format(sigma))
     taps = [gauss_taps(s) for s in sig]
     dev = vol.dev
-    out = _pooled_volume(dev, vol.shape, vol.dtype)
-    nbytes = vol.size * 4
-    tmp = _pool_alloc(dev, nbytes) if sum(len(t) > 0 for t in taps) >= 2 else None
     args = []
     for t in taps:
         args += [t.ctypes.data_as(C.c_void_p) if len(t) else None, (len(t) - 1) // 2 if len(t) else 0]
-    try:
+    nbytes = vol.size * 4 if sum(len(t) > 0 for t in taps) >= 2 else None   # one blurred axis needs no scratch volume
+    with _pooled_outputs(dev, (vol.shape, vol.dtype)) as (out,), _pooled_scratch(dev, nbytes) as tmp:
         dev.call("msk_gauss_blur3d", C.c_void_p(vol.ptr), C.c_void_p(out.ptr), *vol.shape, *args, C.c_void_p(tmp) if tmp else None)
-    except MskError:
-        out.free()
-        raise
-    finally:
-        if tmp:
-            _pool_release(dev, tmp, nbytes)
     return out
 
 
-def upload_pooled(image, dev=None) -> DeviceVolume:
-    """Host volume -> pooled device buffer (loader path of the device augmentations)."""
+def _upload(image, dev, pooled) -> DeviceVolume:
     dev = dev or get_device()
     a = np.asarray(image)
     if a.ndim != 3:
         raise ValueError("expected a 3-D volume, got shape {}".format(a.shape))
     a = np.ascontiguousarray(a, dtype=np.int32 if np.issubdtype(a.dtype, np.integer) else np.float32)
-    v = _pooled_volume(dev, a.shape, a.dtype)
+    v = _new_volume(dev, a.shape, a.dtype, pooled)
     dev.h2d(v.ptr, a)
     return v
 
 
+def upload_pooled(image, dev=None) -> DeviceVolume:
+    """Host volume -> pooled device buffer (loader path of the device augmentations)."""
+    return _upload(image, dev, True)
+
+
 def upload(image, dev=None) -> DeviceVolume:
-    dev = dev or get_device()
-    a = np.asarray(image)
-    if a.ndim != 3:
-        raise ValueError("expected a 3-D volume, got shape {}".format(a.shape))
-    if np.issubdtype(a.dtype, np.integer):
-        a = np.ascontiguousarray(a, dtype=np.int32)
-    else:
-        a = np.ascontiguousarray(a, dtype=np.float32)
-    ptr = dev.malloc(a.nbytes)
-    dev.h2d(ptr, a)
-    return DeviceVolume(dev, ptr, a.shape, a.dtype)
+    """Host volume (integers as int32, anything else as float32) -> device volume of its own allocation."""
+    return _upload(image, dev, False)
 
 
 def resample_device(vol: DeviceVolume, new_shape, order=1, pooled=False) -> DeviceVolume:
@@ -345,12 +335,8 @@ def resample_device(vol: DeviceVolume, new_shape, order=1, pooled=False) -> Devi
     new_shape = tuple(int(s) for s in new_shape)
     if order not in (0, 1):
         raise ValueError("only order 0 and 1 are built (the orders the reference pipelines use)")
-    if pooled:
-        res = _pooled_volume(dev, new_shape, vol.dtype)
-    else:
-        res = DeviceVolume(dev, dev.malloc(int(np.prod(new_shape)) * 4), new_shape, vol.dtype)
-    dev.call("msk_resample3d", C.c_void_p(vol.ptr), *vol.shape, C.c_void_p(res.ptr), *new_shape, int(order),
-             0 if vol.dtype == np.float32 else 1)
+    res = _new_volume(dev, new_shape, vol.dtype, pooled)
+    dev.call("msk_resample3d", C.c_void_p(vol.ptr), *vol.shape, C.c_void_p(res.ptr), *new_shape, int(order), _dt(vol))
     return res
 
 
@@ -376,34 +362,42 @@ def resample(image, spacing=None, new_spacing=[1.0, 1.0, 1.0], new_shape=None, o
     return res, new_spacing
 
 
-def HUnorm(image, HU_min=-1200, HU_max=600, HU_nan=-2000):
-    """reference values.py:67-87."""
-    vol = upload(np.asarray(image, dtype=np.float32))
+def HUnorm_device(vol: DeviceVolume, HU_min=-1200, HU_max=600, HU_nan=-2000) -> DeviceVolume:
+    """reference values.py:67-87, in place."""
     vol.dev.call("msk_hu_norm", C.c_void_p(vol.ptr), C.c_void_p(vol.ptr), C.c_size_t(vol.size), C.c_float(HU_min),
                  C.c_float(HU_max), C.c_float(HU_nan))
-    out = vol.numpy()
+    return vol
+
+
+def normalize_device(vol: DeviceVolume, min_val=None, max_val=None) -> DeviceVolume:
+    """reference values.py:54-64, in place."""
+    use = 0 if (min_val is None and max_val is None) else 1
+    vol.dev.call("msk_minmax_norm", C.c_void_p(vol.ptr), C.c_void_p(vol.ptr), C.c_size_t(vol.size), use,
+                 C.c_float(min_val or 0.0), C.c_float(max_val or 0.0))
+    return vol
+
+
+def _on_host_array(op, image, *args):
+    """a float32 copy of `image` through one in-place device op and back"""
+    vol = upload(np.asarray(image, dtype=np.float32))
+    out = op(vol, *args).numpy()
     vol.free()
     return out
+
+
+def HUnorm(image, HU_min=-1200, HU_max=600, HU_nan=-2000):
+    """reference values.py:67-87."""
+    return _on_host_array(HUnorm_device, image, HU_min, HU_max, HU_nan)
 
 
 def normalize(image, min_val=None, max_val=None):
     """reference values.py:54-64."""
-    vol = upload(np.asarray(image, dtype=np.float32))
-    use = 0 if (min_val is None and max_val is None) else 1
-    vol.dev.call("msk_minmax_norm", C.c_void_p(vol.ptr), C.c_void_p(vol.ptr), C.c_size_t(vol.size), use,
-                 C.c_float(min_val or 0.0), C.c_float(max_val or 0.0))
-    out = vol.numpy()
-    vol.free()
-    return out
+    return _on_host_array(normalize_device, image, min_val, max_val)
 
 
 def max_normalize(image):
     """transforms/transform.py:67-69: im/im.max() if max > 0, plus the channel axis."""
-    vol = upload(np.asarray(image, dtype=np.float32))
-    vol.dev.call("msk_max_norm", C.c_void_p(vol.ptr), C.c_void_p(vol.ptr), C.c_size_t(vol.size))
-    out = vol.numpy()
-    vol.free()
-    return np.expand_dims(out, axis=0)
+    return np.expand_dims(_on_host_array(max_normalize_device, image), axis=0)
 
 
 def label_remap(label, map_dict=None):
@@ -468,10 +462,7 @@ class DevicePipeline:
         else:
             dev.sync()  # the previous copy out of the staging buffer must have drained
         C.memmove(self._pinned[0], a.ctypes.data, a.nbytes)
-        if self.pooled:
-            vol = _pooled_volume(dev, a.shape, a.dtype)
-        else:
-            vol = DeviceVolume(dev, dev.malloc(a.nbytes), a.shape, a.dtype)
+        vol = _new_volume(dev, a.shape, a.dtype, self.pooled)
         dev.call("msk_h2d_async", C.c_void_p(vol.ptr), C.c_void_p(self._pinned[0]), C.c_size_t(a.nbytes))
         return vol
 
@@ -482,10 +473,7 @@ class DevicePipeline:
         dev = self.dev
         dtype = np.dtype(dtype)
         nbytes = int(np.prod(shape)) * 4
-        if self.pooled:
-            vol = _pooled_volume(dev, shape, dtype)
-        else:
-            vol = DeviceVolume(dev, dev.malloc(nbytes), shape, dtype)
+        vol = _new_volume(dev, shape, dtype, self.pooled)
         dev.call("msk_h2d_async", C.c_void_p(vol.ptr), C.c_void_p(pinned_ptr), C.c_size_t(nbytes))
         return _Chain(self, vol)
 
@@ -501,16 +489,11 @@ class _Chain:
         self.pipe, self.vol = pipe, vol
 
     def HUnorm(self, HU_min=-1200, HU_max=600, HU_nan=-2000):
-        v = self.vol
-        v.dev.call("msk_hu_norm", C.c_void_p(v.ptr), C.c_void_p(v.ptr), C.c_size_t(v.size), C.c_float(HU_min),
-                   C.c_float(HU_max), C.c_float(HU_nan))
+        HUnorm_device(self.vol, HU_min, HU_max, HU_nan)
         return self
 
     def normalize(self, min_val=None, max_val=None):
-        v = self.vol
-        use = 0 if (min_val is None and max_val is None) else 1
-        v.dev.call("msk_minmax_norm", C.c_void_p(v.ptr), C.c_void_p(v.ptr), C.c_size_t(v.size), use,
-                   C.c_float(min_val or 0.0), C.c_float(max_val or 0.0))
+        normalize_device(self.vol, min_val, max_val)
         return self
 
     def resample(self, new_shape, order=1):
@@ -521,8 +504,7 @@ class _Chain:
         return self
 
     def max_normalize(self):
-        v = self.vol
-        v.dev.call("msk_max_norm", C.c_void_p(v.ptr), C.c_void_p(v.ptr), C.c_size_t(v.size))
+        max_normalize_device(self.vol)
         return self
 
     def tensor(self):

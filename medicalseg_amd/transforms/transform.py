@@ -346,17 +346,28 @@ class RandomPatchCrop3D:
             rec = [_patch_origin(ro, dim, None, w) for ro, dim, w in zip(self.size, shape, words[3:6])] + [-1, -1, -1, -1, 0]
         return rec
 
+    def _device_crops(self, img, label, sel):
+        """the plain patch of the image and of the label (or None) at the origin of the record `sel`"""
+        from ..preprocess import patch_crop_device
+        return (patch_crop_device(img, sel, self.size, self.pad_value),
+                None if label is None else patch_crop_device(label, sel, self.size, self.label_pad))
+
+    def _device_call(self, img, label, words, cut):
+        """device path: msk_patch_select, then cut(img, label, sel) -> (patch, label patch or None); the record goes back to
+        the pool whether or not the cut is refused, the inputs only once both patches exist"""
+        from ..preprocess import patch_select_device
+        sel = patch_select_device(img if label is None else label, self.size, self.num_classes,
+                                  [] if label is None else self.classes, words)
+        try:
+            out, out_label = cut(img, label, sel)
+        finally:
+            sel.free()
+        return _swap(img, out), None if label is None else _swap(label, out_label)
+
     def __call__(self, img, label=None):
         words = self.get_params(label is not None)
         if _on_device(img):
-            from ..preprocess import patch_crop_device, patch_select_device
-            sel = patch_select_device(img if label is None else label, self.size, self.num_classes,
-                                      [] if label is None else self.classes, words)
-            img = _swap(img, patch_crop_device(img, sel, self.size, self.pad_value))
-            if label is not None:
-                label = _swap(label, patch_crop_device(label, sel, self.size, self.label_pad))
-            sel.free()
-            return img, label
+            return self._device_call(img, label, words, self._device_crops)
         origin = self.select(img.shape[:3], label, words)[:3]
         img = _patch_crop_host(img, origin, self.size, self.pad_value)
         if label is not None:
@@ -765,6 +776,12 @@ class RandomAffinePatchCrop3D(RandomPatchCrop3D):
         self.scale = _check_range(scale, "scale", lowest=0.25, highest=4.0)
         self.per_axis_scale = bool(per_axis_scale)
 
+    def _device_affine(self, img, label, sel, m):
+        from ..preprocess import affine_patch_device
+        if label is None:
+            return affine_patch_device(img, None, sel, self.size, m, self.pad_value), None
+        return affine_patch_device(img, label, sel, self.size, m, self.pad_value, self.label_pad)
+
     def get_matrix(self):
         """the nine draws -> the float32 matrix, or None when neither coin hit"""
         u = [random.random() for _ in range(9)]
@@ -780,20 +797,9 @@ class RandomAffinePatchCrop3D(RandomPatchCrop3D):
         words = self.get_params(label is not None)
         m = self.get_matrix()
         if _on_device(img):
-            from ..preprocess import affine_patch_device, patch_crop_device, patch_select_device
-            sel = patch_select_device(img if label is None else label, self.size, self.num_classes,
-                                      [] if label is None else self.classes, words)
-            try:
-                if m is None:                # neither coin hit: the parent's two crops, msk_affine_patch is not launched
-                    out = patch_crop_device(img, sel, self.size, self.pad_value)
-                    out_label = None if label is None else patch_crop_device(label, sel, self.size, self.label_pad)
-                elif label is None:
-                    out, out_label = affine_patch_device(img, None, sel, self.size, m, self.pad_value), None
-                else:
-                    out, out_label = affine_patch_device(img, label, sel, self.size, m, self.pad_value, self.label_pad)
-            finally:
-                sel.free()
-            return _swap(img, out), None if label is None else _swap(label, out_label)
+            if m is None:                    # neither coin hit: the parent's two crops, msk_affine_patch is not launched
+                return self._device_call(img, label, words, self._device_crops)
+            return self._device_call(img, label, words, lambda *a: self._device_affine(*a, m))
         origin = self.select(img.shape[:3], label, words)[:3]
         if m is None:
             return (_patch_crop_host(img, origin, self.size, self.pad_value),

@@ -84,6 +84,7 @@ NOOP(msk_class_weights) NOOP(msk_loss_fwd) NOOP(msk_loss_bwd) NOOP(msk_sgd_momen
 NOOP(msk_resample3d) NOOP(msk_hu_norm) NOOP(msk_minmax_norm) NOOP(msk_max_norm) NOOP(msk_label_remap)
 NOOP(msk_crop_resample3d) NOOP(msk_flip3d) NOOP(msk_rotate3d)
 NOOP(msk_interp_trilinear_fwd) NOOP(msk_interp_trilinear_bwd)
+NOOP(msk_flip_axes) NOOP(msk_tta_accumulate) NOOP(msk_tta_finish) NOOP(msk_sw_gather) NOOP(msk_sw_accumulate)
 typedef struct { void* p; int32_t n, d, h, w, c, ld; } fake_tensor;
 int msk_interp_scratch_bytes(void* c, fake_tensor s, fake_tensor d, size_t* b) {
   (void)c; *b = ((size_t)d.n * d.d * d.h * s.w + (size_t)d.n * d.d * s.h * s.w) * s.c * 4; return 0;

@@ -276,6 +276,45 @@ def test_transform_device_path_equals_host_path(shape, roi):
         g_lab.free()
 
 
+def test_a_refused_crop_leaves_the_pool_balanced(monkeypatch):
+    """the select's record goes back to the pool when a crop behind it is refused; the caller still owns the two inputs"""
+    from medicalseg_amd import preprocess as pp
+    from medicalseg_amd import transforms as T
+    from medicalseg_amd._lib import MskError
+    shape, roi = (5, 6, 7), (4, 4, 4)
+    iv, lv = pp.upload_pooled(R.image_for(shape, 5)), pp.upload_pooled(R.blobs(shape, 3, 6))
+    balance, selected = [0], []
+    alloc, release, select = pp._pool_alloc, pp._pool_release, pp.patch_select_device
+
+    def counted_alloc(dev_, nbytes):
+        balance[0] += 1
+        return alloc(dev_, nbytes)
+
+    def counted_release(dev_, ptr, nbytes):
+        balance[0] -= 1
+        return release(dev_, ptr, nbytes)
+
+    def recorded_select(*args):
+        selected.append(select(*args))
+        return selected[-1]
+
+    def refused(*args, **kwargs):
+        assert len(selected) == 1                                                  # the select has run
+        raise MskError("msk_patch_crop failed: refused")
+    monkeypatch.setattr(pp, "_pool_alloc", counted_alloc)
+    monkeypatch.setattr(pp, "_pool_release", counted_release)
+    monkeypatch.setattr(pp, "patch_select_device", recorded_select)
+    monkeypatch.setattr(pp, "patch_crop_device", refused)
+    random.seed(0)
+    with pytest.raises(MskError, match="refused"):
+        T.RandomPatchCrop3D(roi, 3, fg_prob=0.5, label_pad=255)(iv, lv)
+    assert balance[0] == 0
+    assert selected[0].ptr is None and iv.ptr and lv.ptr
+    iv.free()
+    lv.free()
+    assert balance[0] == -2
+
+
 class _TwoSizes:
     """two samples of different extents, augmented on the device"""
     shapes = [(9, 30, 37), (14, 20, 25)]

@@ -379,11 +379,19 @@ def test_sliding_release_frees_the_buffers(vnet):
     from medicalseg_amd.core import infer
     from medicalseg_amd.device import to_tensor
     im = to_tensor(R.volume(1, (16, 16, 24), 1, 43))
-    infer.sliding_window_inference(vnet, im, (16, 16, 16))
     dev = im.dev
-    assert dev.__dict__.get("_sw_buffers")
+    infer.tta_release(dev)
     infer.sliding_release(dev)
-    assert "_sw_buffers" not in dev.__dict__
+    assert not dev.kept
+    infer.aug_inference(vnet, to_tensor(R.volume(1, (16, 16, 16), 1, 44)), flip_axes=(2,))
+    tta = dict(dev.kept)
+    assert tta and all(key[0] == "tta" for key in tta)
+    infer.sliding_window_inference(vnet, im, (16, 16, 16))
+    assert any(key[0] == "sw" for key in dev.kept) and len(dev.kept) > len(tta)
+    infer.sliding_release(dev)
+    assert dev.kept == tta                                                       # the other path's buffers stay
+    infer.tta_release(dev)
+    assert not dev.kept
     pred, logits = infer.sliding_window_inference(vnet, im, (16, 16, 16))        # and they come back on demand
     assert logits.shape == (1, 3, 16, 16, 24)
 

@@ -258,6 +258,62 @@ def test_preprocess_wrappers(fake_pkg):
     assert pp.label_remap(np.zeros((2, 3, 4), np.int32), {1: 2}).shape == (2, 3, 4)
 
 
+def test_kept_inference_buffers_are_allocated_once_and_released_per_family(fake_pkg, monkeypatch):
+    """aug_inference and sliding_window_inference keep their device buffers between calls: the second call of each allocates
+    nothing, tta_release and sliding_release each free exactly what their own path allocated and leave the other's, and the
+    buffers come back on demand.  Counted at Device.call; the stand-in computes nothing."""
+    from medicalseg_amd.core import infer
+    from medicalseg_amd.device import Device, Tensor, to_tensor
+    dev = Device(0)
+    counts = {"msk_malloc": 0, "msk_free": 0}
+    real = Device.call
+
+    def counting(self, name, *args):
+        if name in counts:
+            counts[name] += 1
+        return real(self, name, *args)
+    monkeypatch.setattr(Device, "call", counting)
+
+    def model(x):
+        dev.arena.reset()
+        return [Tensor.empty(dev, x.n, x.d, x.h, x.w, 3)]
+
+    def traffic(fn):
+        """(device allocations, frees) of one call"""
+        m, f = counts["msk_malloc"], counts["msk_free"]
+        fn()
+        return counts["msk_malloc"] - m, counts["msk_free"] - f
+
+    small = to_tensor(np.zeros((1, 1, 8, 8, 8), np.float32), dev)
+    big = to_tensor(np.zeros((1, 1, 8, 8, 12), np.float32), dev)
+    model(small)                         # the arena's first block
+
+    def tta():
+        pred, probs, plain = infer.aug_inference(model, small, scales=[1.0, 0.5], flip_axes=(0, 2), with_plain=True)
+        assert pred.shape == (1, 1, 8, 8, 8) and probs.shape == plain.shape == (1, 3, 8, 8, 8)
+
+    def sliding():
+        pred, logits = infer.sliding_window_inference(model, big, (8, 8, 8), sw_batch_size=2)      # two windows, one batch
+        assert pred.shape == (1, 1, 8, 8, 12) and logits.shape == (1, 3, 8, 8, 12)
+        act = Tensor.empty(dev, 1, 8, 8, 12, 1)     # an input in the arena is kept aside before the first forward
+        infer.sliding_window_inference(model, act, (8, 8, 8), sw_batch_size=2)
+
+    # resized 4^3, mirrored 8^3 and 4^3, acc, plain; three plan tables, patches, acc, the kept input
+    assert traffic(tta) == (5, 0) and traffic(sliding) == (6, 0)
+    assert traffic(tta) == (0, 0) and traffic(sliding) == (0, 0)
+    assert traffic(lambda: infer.sliding_release(dev)) == (0, 6)
+    assert traffic(lambda: infer.sliding_release(dev)) == (0, 0)
+    assert traffic(tta) == (0, 0)                   # the other family's buffers are still there
+    assert traffic(sliding) == (6, 0)
+    assert traffic(lambda: infer.tta_release(dev)) == (0, 5)
+    assert traffic(sliding) == (0, 0)
+    assert traffic(lambda: infer.sliding_release(dev)) == (0, 6)
+    assert not dev.kept
+    assert traffic(tta) == (5, 0) and traffic(sliding) == (6, 0)      # and they come back on demand
+    infer.tta_release(dev)
+    infer.sliding_release(dev)
+
+
 def test_train_profiler_options_and_step_protocol(tmp_path):
     """--profiler_options (reference utils/train_profiler.py:26-112): the option grammar, profile on at batch_range[0],
     report + optional exit at batch_range[1]."""
