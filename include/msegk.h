@@ -623,6 +623,37 @@ int msk_adam(msk_ctx* ctx, float* param, const float* grad, float* moment1, floa
              size_t count, float lr, float beta1, float beta2, float epsilon, double beta1_pow,
              double beta2_pow, float weight_decay, float grad_scale);
 
+/* ---- gradient clipping and Nesterov momentum (paddle.nn.ClipGradByGlobalNorm / ClipGradByValue, Momentum(use_nesterov=True):
+ *      the reference hands grad_clip and use_nesterov to paddle.optimizer, cvlibs/config.py:217-224;
+ *      tests/clip_reference.py is the statement) ---- */
+/* Bytes of workspace msk_grad_clip_coef needs for count gradients (in [1, 2^31)): 8 bytes per chunk of 4096.  Needs no context
+ * and no GPU.                                                                                                                */
+int msk_grad_clip_workspace(size_t count, size_t* bytes);
+/* rec (DEVICE, 4 doubles, 8-byte aligned) = {S, norm, coef, 0} of the count float32 of grad (DEVICE, 16-byte aligned: an
+ * arena): S = the sum of the exact (double)g * (double)g in float64 in the FIXED order of msk_intensity_stats -- chunk c covers
+ * [4096c, 4096(c+1)), lane l of 256 adds its 16 terms in ascending order (elements past count add +0.0), the tree v[l] +=
+ * v[l+s], s = 128 .. 1, and the chunk values are reduced by the same scheme;  norm = (double)grad_scale * sqrt(S);  coef =
+ * (float)(clip_norm / norm) if norm > clip_norm, else 1 (clip_norm = +inf measures only), stored as a double.  It first joins
+ * the internal weight-gradient stream, then makes two launches on the context stream: no atomics, no synchronisation, no
+ * download -- the update below reads the record on the device.  workspace (DEVICE): 8-byte aligned, msk_grad_clip_workspace
+ * bytes; its contents mean nothing to the caller.  Argument errors, reported before any launch: null or misaligned pointers,
+ * count outside [1, 2^31), clip_norm NaN or <= 0.                                                                            */
+int msk_grad_clip_coef(msk_ctx* ctx, const float* grad, size_t count, float grad_scale, float clip_norm, void* workspace,
+                       double* rec);
+/* msk_sgd_momentum with Paddle's order clip, L2 decay, momentum:  gs = grad_scale * (float)clip_rec[2] (one float32 product;
+ * clip_rec: DEVICE record of msk_grad_clip_coef, read on the device, or null = 1);  g' = g * gs, clamped to [clip_min,
+ * clip_max] unless both are infinite (a NaN stays a NaN);  t = g' + wd*p;  v = mu*v + t;  p -= lr*v, or with nesterov != 0
+ * p -= lr*(t + mu*v) (paddle's use_nesterov: param - (grad + velocity_out * mu) * lr).  The fmaf chain per element is
+ * msk_sgd_momentum's: with clip_rec null or coef == 1, infinite bounds and nesterov == 0 the results are bitwise its.  One
+ * launch over the whole range behind a join of the weight-gradient stream, then the re-pack of the convolution weights.      */
+int msk_sgd_momentum_clip(msk_ctx* ctx, float* param, const float* grad, float* velocity, size_t count, float lr,
+                          float momentum, float weight_decay, float grad_scale, int nesterov, const double* clip_rec,
+                          float clip_min, float clip_max);
+/* msk_adam on the same g' (clip_rec, clip_min, clip_max as above); bitwise msk_adam when nothing bites.                       */
+int msk_adam_clip(msk_ctx* ctx, float* param, const float* grad, float* moment1, float* moment2, size_t count, float lr,
+                  float beta1, float beta2, float epsilon, double beta1_pow, double beta2_pow, float weight_decay,
+                  float grad_scale, const double* clip_rec, float clip_min, float clip_max);
+
 /* ---- preprocessing (tools/preprocess_utils) ----------------------------------- */
 /* geometry.py:31-69 resample == scipy.ndimage.zoom(order 0|1, grid_mode=False):
  * align-corner coordinate map; order 0 = floor(c+0.5), order 1 = trilinear.

@@ -155,6 +155,10 @@ SIGNATURES = {
     "msk_sgd_momentum_eager": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_finish": (_i, [_vp]),
     "msk_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _d, _d, _f, _f]),
+    "msk_grad_clip_workspace": (_i, [_sz, C.POINTER(_sz)]),
+    "msk_grad_clip_coef": (_i, [_vp, _vp, _sz, _f, _f, _vp, _vp]),
+    "msk_sgd_momentum_clip": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _vp, _f, _f]),
+    "msk_adam_clip": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _d, _d, _f, _f, _vp, _f, _f]),
     "msk_resample3d": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "msk_crop_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "msk_flip3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),

@@ -22,6 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import NULL_TENSOR, MskBnFin, MskConvDesc, MskError
 from .device import Tensor, get_device
+from .optimizer import ClipGradByGlobalNorm, ClipGradByNorm, ClipGradByValue  # noqa: F401  (paddle.nn.ClipGradBy*)
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.9

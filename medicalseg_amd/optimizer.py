@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-__all__ = ["Momentum", "SGD", "Adam", "lr"]
+__all__ = ["Momentum", "SGD", "Adam", "lr", "ClipGradByGlobalNorm", "ClipGradByValue", "ClipGradByNorm"]
 OPTIMIZERS = ("Momentum", "SGD", "Adam")     # names accepted as an optimizer `type` (cvlibs/config.py); `lr` is the scheduler namespace
 
 
@@ -18,6 +18,91 @@ def _warn_unused(cls_name, kw):
         import warnings
         warnings.warn("%s: option(s) %s are not implemented by medicalseg_amd and are IGNORED" % (cls_name, sorted(kw)))
 
+
+class ClipGradByGlobalNorm:
+    """paddle.nn.ClipGradByGlobalNorm(clip_norm): every gradient times clip_norm / max(global L2 norm, clip_norm).  The norm
+    is one reduction over the flat gradient arena (msk_grad_clip_coef) whose result stays on the device."""
+
+    def __init__(self, clip_norm, group_name="default_group", auto_skip_clip=False):
+        self.clip_norm = float(clip_norm)
+        if not self.clip_norm > 0.0:
+            raise ValueError("clip_norm must be > 0 (inf measures the norm without clipping), got %r" % (clip_norm,))
+
+
+class ClipGradByValue:
+    """paddle.nn.ClipGradByValue(max, min=None): every gradient element limited to [min, max]; min defaults to -max."""
+
+    def __init__(self, max, min=None):
+        self.max = float(max)
+        self.min = -self.max if min is None else float(min)
+        if not self.min <= self.max:
+            raise ValueError("ClipGradByValue needs min <= max, got [%r, %r]" % (self.min, self.max))
+
+
+class ClipGradByNorm:
+    """paddle.nn.ClipGradByNorm(clip_norm) limits the norm of EACH tensor: not built (the arena kernels have no per-tensor
+    form); an optimizer given one raises instead of training something else."""
+
+    def __init__(self, clip_norm):
+        self.clip_norm = float(clip_norm)
+
+
+_CLIPS = {c.__name__: c for c in (ClipGradByGlobalNorm, ClipGradByValue, ClipGradByNorm)}
+
+
+def _make_clip(spec):
+    """grad_clip as the optimizers take it: None, one of the classes above, or the YAML spelling
+    {type: ClipGradByGlobalNorm, clip_norm: 12}"""
+    if isinstance(spec, dict):
+        args = dict(spec)
+        kind = args.pop("type", None)
+        if kind not in _CLIPS:
+            raise ValueError("grad_clip: unknown type %r (one of %s)" % (kind, sorted(_CLIPS)))
+        spec = _CLIPS[kind](**args)
+    if isinstance(spec, ClipGradByNorm):
+        raise NotImplementedError("grad_clip=ClipGradByNorm: per-tensor clipping is not built by medicalseg_amd; use "
+                                  "ClipGradByGlobalNorm or ClipGradByValue")
+    if spec is not None and not isinstance(spec, (ClipGradByGlobalNorm, ClipGradByValue)):
+        raise TypeError("grad_clip must be None, ClipGradByGlobalNorm, ClipGradByValue or a dict {type: ..., ...}, got %r"
+                        % (spec,))
+    return spec
+
+
+class _ClipState:
+    """What an optimizer with grad_clip / use_nesterov keeps: the clip object and, for a global-norm clip, the device
+    record {S, norm, coef, 0} and the reduction's workspace, allocated once."""
+
+    def __init__(self, arena, clip):
+        self.clip = clip
+        self.rec_ptr = self.ws_ptr = None
+        self.stepped = False
+        self.lo, self.hi = (clip.min, clip.max) if isinstance(clip, ClipGradByValue) else (-math.inf, math.inf)
+        if isinstance(clip, ClipGradByGlobalNorm):
+            dev = arena.dev
+            nbytes = C.c_size_t(0)
+            if dev.lib.msk_grad_clip_workspace(C.c_size_t(arena.count), C.byref(nbytes)) != 0:
+                raise ValueError("msk_grad_clip_workspace refused an arena of %d floats" % arena.count)
+            self.rec_ptr, self.ws_ptr = dev.malloc(32), dev.malloc(nbytes.value)
+            dev.memset(self.rec_ptr, 0, 32)
+
+    def measure(self, arena):
+        """enqueue the norm and the coefficient of the gradients as they are now; returns the record (or None)"""
+        if self.rec_ptr is not None:
+            arena.dev.call("msk_grad_clip_coef", C.c_void_p(arena.grad_ptr), C.c_size_t(arena.count), C.c_float(arena.grad_scale),
+                           C.c_float(self.clip.clip_norm), C.c_void_p(self.ws_ptr), C.c_void_p(self.rec_ptr))
+            self.stepped = True
+        return C.c_void_p(self.rec_ptr) if self.rec_ptr is not None else None
+
+    def grad_norm(self, dev):
+        if self.rec_ptr is None or not self.stepped:
+            return None
+        return float(dev.d2h(self.rec_ptr, (4,), np.float64)[1])
+
+
+def _grad_norm(self):
+    """The global L2 norm of the (scaled) gradients the last clipped step saw, as a float; None before the first such step or
+    without a global-norm clip.  Downloads the record, so it synchronises: for logging and tests."""
+    return self._clip.grad_norm(self.arena.dev) if self._clip is not None else None
 
 
 class _LR:
@@ -91,10 +176,14 @@ class Momentum:
     """paddle.optimizer.Momentum(lr, parameters, momentum, weight_decay: float = L2):
     g += wd*p; v = mu*v + g; p -= lr*v on EVERY trainable tensor (BN, PReLU, biases
     included -- App. B.8 v).  All parameters live in one flat arena, so a step is a single
-    kernel over 45.6 M floats (K10)."""
+    kernel over 45.6 M floats (K10).  use_nesterov=True: p -= lr*(g + mu*v) with the new v.  grad_clip: ClipGradByGlobalNorm /
+    ClipGradByValue (or their YAML dict), applied before the L2 term as Paddle does; the norm and the clip coefficient stay
+    on the device (msk_grad_clip_coef -> msk_sgd_momentum_clip).  With neither option the calls are what they always were."""
 
-    def __init__(self, learning_rate=0.001, momentum=0.9, parameters=None, weight_decay=None, **kw):
+    def __init__(self, learning_rate=0.001, momentum=0.9, parameters=None, weight_decay=None, use_nesterov=False,
+                 grad_clip=None, **kw):
         _warn_unused(type(self).__name__, kw)
+        grad_clip = _make_clip(grad_clip)
         if not parameters:
             raise ValueError("parameters must be a non-empty list")
         # tensors no forward path reaches get no gradient and are skipped by paddle's optimizer
@@ -110,8 +199,12 @@ class Momentum:
         dev = self.arena.dev
         self.velocity_ptr = dev.malloc(max(self.arena.count, 4) * 4)
         dev.memset(self.velocity_ptr, 0, max(self.arena.count, 4) * 4)
+        # either option moves step() to msk_grad_clip_coef + msk_sgd_momentum_clip; with neither, nothing below changes
+        self.use_nesterov = bool(use_nesterov)
+        self._clip = _ClipState(self.arena, grad_clip) if (self.use_nesterov or grad_clip is not None) else None
 
         self._eager = False
+        self._eager_refused = False   # enable_eager said once why it stays off
         self.eager_min_floats = int(os.environ.get("MSEGK_EAGER_MIN_FLOATS", 1 << 20))   # blocks below this stay with step() (launch count; A/B: 0 = every block)
         self._eager_done = []     # [(lo, hi)] slices of the arena already updated during this backward pass
 
@@ -135,6 +228,13 @@ class Momentum:
         gradients are final after the all-reduce, not after backward.  core.train() and bench.py switch it on at one rank."""
         if not on:
             self._eager = False
+            return False
+        if self._clip is not None:
+            if not self._eager_refused:
+                from .utils import logger
+                logger.info("optimizer: eager mode stays off with grad_clip / use_nesterov -- the global norm needs every "
+                            "gradient and the eager entry point has no Nesterov form; step() updates the whole arena")
+            self._eager_refused = True
             return False
         if getattr(model, "arena", None) is not self.arena or not hasattr(model, "_grad_ready_hooks"):
             return False
@@ -188,6 +288,13 @@ class Momentum:
 
     def step(self):
         a = self.arena
+        if self._clip is not None:
+            rec = self._clip.measure(a)
+            a.dev.call("msk_sgd_momentum_clip", C.c_void_p(a.value_ptr), C.c_void_p(a.grad_ptr), C.c_void_p(self.velocity_ptr),
+                       C.c_size_t(a.count), C.c_float(self.get_lr()), C.c_float(self.momentum), C.c_float(self.weight_decay),
+                       C.c_float(a.grad_scale), C.c_int(1 if self.use_nesterov else 0), rec, C.c_float(self._clip.lo),
+                       C.c_float(self._clip.hi))
+            return
         if self._eager_done:
             # what the hooks did not cover (parameters outside the reported blocks), then the join
             done, self._eager_done = sorted(self._eager_done), []
@@ -203,6 +310,8 @@ class Momentum:
         a.dev.call("msk_sgd_momentum", C.c_void_p(a.value_ptr), C.c_void_p(a.grad_ptr), C.c_void_p(self.velocity_ptr),
                    C.c_size_t(a.count), C.c_float(self.get_lr()), C.c_float(self.momentum),
                    C.c_float(self.weight_decay), C.c_float(a.grad_scale))
+
+    grad_norm = _grad_norm
 
     def clear_grad(self):
         self.arena.zero_grad()
@@ -262,8 +371,8 @@ class Momentum:
 
 
 class SGD(Momentum):
-    def __init__(self, learning_rate=0.001, parameters=None, weight_decay=None, **kw):
-        super().__init__(learning_rate, 0.0, parameters, weight_decay, **kw)
+    def __init__(self, learning_rate=0.001, parameters=None, weight_decay=None, use_nesterov=False, grad_clip=None, **kw):
+        super().__init__(learning_rate, 0.0, parameters, weight_decay, use_nesterov=use_nesterov, grad_clip=grad_clip, **kw)
 
 
 class Adam:
@@ -273,8 +382,9 @@ class Adam:
     identical for every tensor because all tensors step together)."""
 
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, parameters=None, weight_decay=None,
-                 **kw):
+                 grad_clip=None, **kw):
         _warn_unused("Adam", kw)
+        grad_clip = _make_clip(grad_clip)
         if not parameters:
             raise ValueError("parameters must be a non-empty list")
         parameters = [p for p in parameters if not getattr(p, "frozen", False)]
@@ -292,12 +402,24 @@ class Adam:
         self.moment1_ptr, self.moment2_ptr = dev.malloc(n), dev.malloc(n)
         dev.memset(self.moment1_ptr, 0, n)
         dev.memset(self.moment2_ptr, 0, n)
+        self._clip = _ClipState(self.arena, grad_clip) if grad_clip is not None else None
 
     get_lr = Momentum.get_lr
     set_lr = Momentum.set_lr
+    grad_norm = _grad_norm
 
     def step(self):
         a = self.arena
+        if self._clip is not None:
+            rec = self._clip.measure(a)
+            a.dev.call("msk_adam_clip", C.c_void_p(a.value_ptr), C.c_void_p(a.grad_ptr), C.c_void_p(self.moment1_ptr),
+                       C.c_void_p(self.moment2_ptr), C.c_size_t(a.count), C.c_float(self.get_lr()), C.c_float(self.beta1),
+                       C.c_float(self.beta2), C.c_float(self.epsilon), C.c_double(self.beta1_pow),
+                       C.c_double(self.beta2_pow), C.c_float(self.weight_decay), C.c_float(a.grad_scale), rec,
+                       C.c_float(self._clip.lo), C.c_float(self._clip.hi))
+            self.beta1_pow *= self.beta1
+            self.beta2_pow *= self.beta2
+            return
         a.dev.call("msk_adam", C.c_void_p(a.value_ptr), C.c_void_p(a.grad_ptr), C.c_void_p(self.moment1_ptr),
                    C.c_void_p(self.moment2_ptr), C.c_size_t(a.count), C.c_float(self.get_lr()), C.c_float(self.beta1),
                    C.c_float(self.beta2), C.c_float(self.epsilon), C.c_double(self.beta1_pow),
