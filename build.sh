@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Imedicalseg_amd/csr
 OBJS=""
 for f in medicalseg_amd/csrc/*.hip; do
   o=build/$(basename ${f%.hip}).o
-  if [ ! -f $o ] || [ $f -nt $o ] || [ include/msegk.h -nt $o ] || [ medicalseg_amd/csrc/msk_common.h -nt $o ] || [ medicalseg_amd/csrc/msk_conv.h -nt $o ] || [ medicalseg_amd/csrc/msk_wbf.h -nt $o ]; then
+  if [ ! -f $o ] || [ $f -nt $o ] || [ include/msegk.h -nt $o ] || [ medicalseg_amd/csrc/msk_common.h -nt $o ] || [ medicalseg_amd/csrc/msk_device.h -nt $o ] || [ medicalseg_amd/csrc/msk_conv.h -nt $o ] || [ medicalseg_amd/csrc/msk_wbf.h -nt $o ]; then
     rm -f $o   # a failed compile must not leave the previous object behind (the jobs run in the background)
     hipcc $FLAGS $EXTRA -c $f -o $o &
   fi
@@ -24,7 +24,7 @@ echo "built $OUT/libmsegk.so"
 # test build: the same objects, msk_dp.hip recompiled with the host transport (two ranks as two processes on ONE GPU,
 # tests/test_gpu_dp2.py) -- the release library does not contain it
 T=build/msk_dp_test.o
-if [ ! -f $T ] || [ medicalseg_amd/csrc/msk_dp.hip -nt $T ] || [ medicalseg_amd/csrc/msk_common.h -nt $T ] || [ include/msegk.h -nt $T ]; then
+if [ ! -f $T ] || [ medicalseg_amd/csrc/msk_dp.hip -nt $T ] || [ medicalseg_amd/csrc/msk_common.h -nt $T ] || [ medicalseg_amd/csrc/msk_device.h -nt $T ] || [ include/msegk.h -nt $T ]; then
   hipcc $FLAGS $EXTRA -DMSK_TEST_TRANSPORT -c medicalseg_amd/csrc/msk_dp.hip -o $T
 fi
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libmsegk_test.so ${OBJS/build\/msk_dp.o/$T} -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

@@ -119,12 +119,6 @@ affine_tile_k(const float* __restrict__ img, const int32_t* __restrict__ label, 
 inline bool extents_ok(int d, int h, int w) {
   return d >= 1 && h >= 1 && w >= 1 && d <= kMaxExtent && h <= kMaxExtent && w <= kMaxExtent;
 }
-inline bool below_2_31(int d, int h, int w) { return (long)d * h * w <= 0x7fffffffL; }
-inline bool disjoint(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 + abytes <= b0 || b0 + bbytes <= a0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -137,7 +131,7 @@ int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d
   MSK_REQUIRE(ctx, ((((uintptr_t)img) | ((uintptr_t)label) | ((uintptr_t)sel) | ((uintptr_t)out_img) | ((uintptr_t)out_label)) & 3) == 0,
               "img / label / sel / out_img / out_label must be 4-byte aligned");
   MSK_REQUIRE(ctx, extents_ok(d, h, w) && extents_ok(rd, rh, rw), "volume and patch extents must be in [1, 8192]");
-  MSK_REQUIRE(ctx, below_2_31(d, h, w) && below_2_31(rd, rh, rw), "volume and patch must have fewer than 2^31 voxels each");
+  MSK_REQUIRE(ctx, msk_below_2_31(d, h, w) && msk_below_2_31(rd, rh, rw), "volume and patch must have fewer than 2^31 voxels each");
   AffineArgs g;
   for (int i = 0; i < 9; ++i) {
     // written so that a NaN fails: |m| <= 4 is false for it
@@ -145,12 +139,12 @@ int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d
     g.m[i] = matrix[i];
   }
   const size_t vbytes = (size_t)d * h * w * 4, pbytes = (size_t)rd * rh * rw * 4;
-  MSK_REQUIRE(ctx, disjoint(out_img, pbytes, img, vbytes) && disjoint(out_img, pbytes, sel, 12), "out_img must not overlap img or sel");
+  MSK_REQUIRE(ctx, msk_bytes_disjoint(out_img, pbytes, img, vbytes) && msk_bytes_disjoint(out_img, pbytes, sel, 12), "out_img must not overlap img or sel");
   if (label != nullptr) {
-    MSK_REQUIRE(ctx, disjoint(out_img, pbytes, label, vbytes), "out_img must not overlap label");
-    MSK_REQUIRE(ctx, disjoint(out_label, pbytes, img, vbytes) && disjoint(out_label, pbytes, label, vbytes) &&
-                         disjoint(out_label, pbytes, sel, 12), "out_label must not overlap img, label or sel");
-    MSK_REQUIRE(ctx, disjoint(out_label, pbytes, out_img, pbytes), "out_label must not overlap out_img");
+    MSK_REQUIRE(ctx, msk_bytes_disjoint(out_img, pbytes, label, vbytes), "out_img must not overlap label");
+    MSK_REQUIRE(ctx, msk_bytes_disjoint(out_label, pbytes, img, vbytes) && msk_bytes_disjoint(out_label, pbytes, label, vbytes) &&
+                         msk_bytes_disjoint(out_label, pbytes, sel, 12), "out_label must not overlap img, label or sel");
+    MSK_REQUIRE(ctx, msk_bytes_disjoint(out_label, pbytes, out_img, pbytes), "out_label must not overlap out_img");
   }
   g.D = d; g.H = h; g.W = w;
   g.rd = rd; g.rh = rh; g.rw = rw;

@@ -29,39 +29,6 @@ constexpr int kScanTile = 4 * kScanThreads; // histogram entries per workgroup o
 constexpr uint32_t kScoreMask = 0x7fffffffu;
 constexpr uint32_t kNone = 0xffffffffu;
 
-// ---- scans over a workgroup ----------------------------------------------------------------------------------
-struct OpAdd { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
-struct OpMax { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
-struct OpMin { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
-
-// Exclusive scan of one value per thread in thread order (REV: in reverse thread order, i.e. over the threads behind this
-// one); *total = the combination of all threads.  wtot: one LDS word per wavefront, reusable after the call returns.
-template <bool REV, class Op>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t identity, Op op, uint32_t* wtot, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int src = REV ? lane + o : lane - o;
-    const uint32_t t = __shfl(inc, src & 63, 64);
-    if (src >= 0 && src < 64) inc = op(inc, t);
-  }
-  const int nb = REV ? lane + 1 : lane - 1;
-  const uint32_t left = __shfl(inc, nb & 63, 64);
-  uint32_t ex = (nb >= 0 && nb < 64) ? left : identity;
-  __syncthreads();   // the previous use of wtot is over
-  if (lane == (REV ? 0 : 63)) wtot[wave] = inc;
-  __syncthreads();
-  uint32_t before = identity, all = identity;
-  for (int w = 0; w < nw; ++w) {
-    const uint32_t t = wtot[w];
-    all = op(all, t);
-    if (REV ? w > wave : w < wave) before = op(before, t);
-  }
-  *total = all;
-  return op(before, ex);
-}
-
 // ---- pack ----------------------------------------------------------------------------------------------------
 // grid-stride over tiles of tv voxels; dynamic LDS: tv * (C | 1) words
 __global__ void __launch_bounds__(kThreads)
@@ -160,7 +127,7 @@ auc_scan_tiles_k(uint32_t* __restrict__ hist, int total, int npart, uint32_t* __
     s += v[j];
   }
   uint32_t all;
-  uint32_t run = block_excl_scan<false>(s, 0u, OpAdd(), wtot, &all);
+  uint32_t run = msk_block_excl_scan<false>(s, 0u, msk_op_add(), wtot, &all);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (base + j < total) h[base + j] = run;
@@ -179,7 +146,7 @@ auc_scan_parts_k(uint32_t* __restrict__ part, int npart) {
     const int i = base + threadIdx.x;
     const uint32_t v = i < npart ? p[i] : 0;
     uint32_t all;
-    const uint32_t ex = block_excl_scan<false>(v, 0u, OpAdd(), wtot, &all);
+    const uint32_t ex = msk_block_excl_scan<false>(v, 0u, msk_op_add(), wtot, &all);
     if (i < npart) p[i] = carry + ex;
     carry += all;
   }
@@ -282,12 +249,12 @@ auc_blocks_k(const uint32_t* __restrict__ keys, size_t stride, int count, int nb
   uint32_t negm, posm, headm;
   load_flags(kc, count, (long)blockIdx.x * kChunk + (long)threadIdx.x * kIpt, negm, posm, headm);
   uint32_t nneg;
-  const uint32_t ex = block_excl_scan<false>((uint32_t)__popc(negm), 0u, OpAdd(), wtot, &nneg);
+  const uint32_t ex = msk_block_excl_scan<false>((uint32_t)__popc(negm), 0u, msk_op_add(), wtot, &nneg);
   const uint32_t last = headm ? ex + below(negm, 31 - __clz((int)headm)) + 1u : 0u;
   const uint32_t first = headm ? ex + below(negm, __ffs((int)headm) - 1) : kNone;
   uint32_t lastmax, firstmin;
-  block_excl_scan<false>(last, 0u, OpMax(), wtot, &lastmax);
-  block_excl_scan<false>(first, kNone, OpMin(), wtot, &firstmin);
+  msk_block_excl_scan<false>(last, 0u, msk_op_max(), wtot, &lastmax);
+  msk_block_excl_scan<false>(first, kNone, msk_op_min(), wtot, &firstmin);
   if (threadIdx.x == 0) {
     uint32_t* b = blk + (size_t)blockIdx.y * 3 * nb;
     b[blockIdx.x] = nneg;
@@ -310,7 +277,7 @@ auc_carry_k(uint32_t* __restrict__ blk, int nb, int count, unsigned long long* _
   uint32_t s = 0;
   for (int b = b0; b < b1; ++b) s += base[b];
   uint32_t nneg;
-  uint32_t run = block_excl_scan<false>(s, 0u, OpAdd(), wtot, &nneg);
+  uint32_t run = msk_block_excl_scan<false>(s, 0u, msk_op_add(), wtot, &nneg);
   uint32_t segmax = 0, segmin = kNone;
   for (int b = b0; b < b1; ++b) {   // local head values -> values of N
     const uint32_t n = base[b], l = lastv[b], f = firstv[b];
@@ -327,8 +294,8 @@ auc_carry_k(uint32_t* __restrict__ blk, int nb, int count, unsigned long long* _
     run += n;
   }
   uint32_t all;
-  uint32_t fwd = block_excl_scan<false>(segmax, 0u, OpMax(), wtot, &all);
-  uint32_t bwd = block_excl_scan<true>(segmin, kNone, OpMin(), wtot, &all);
+  uint32_t fwd = msk_block_excl_scan<false>(segmax, 0u, msk_op_max(), wtot, &all);
+  uint32_t bwd = msk_block_excl_scan<true>(segmin, kNone, msk_op_min(), wtot, &all);
   for (int b = b0; b < b1; ++b) {
     const uint32_t l = lastv[b];
     lastv[b] = fwd;
@@ -357,11 +324,11 @@ auc_sum_k(const uint32_t* __restrict__ keys, size_t stride, int count, int nb, c
   uint32_t negm, posm, headm;
   load_flags(kc, count, (long)blockIdx.x * kChunk + (long)threadIdx.x * kIpt, negm, posm, headm);
   uint32_t all;
-  const uint32_t n0 = b[blockIdx.x] + block_excl_scan<false>((uint32_t)__popc(negm), 0u, OpAdd(), wtot, &all);   // N of the thread's first key
+  const uint32_t n0 = b[blockIdx.x] + msk_block_excl_scan<false>((uint32_t)__popc(negm), 0u, msk_op_add(), wtot, &all);   // N of the thread's first key
   const uint32_t last = headm ? n0 + below(negm, 31 - __clz((int)headm)) : 0u;
   const uint32_t first = headm ? n0 + below(negm, __ffs((int)headm) - 1) : kNone;
-  uint32_t na = block_excl_scan<false>(last, 0u, OpMax(), wtot, &all);
-  uint32_t nbk = block_excl_scan<true>(first, kNone, OpMin(), wtot, &all);
+  uint32_t na = msk_block_excl_scan<false>(last, 0u, msk_op_max(), wtot, &all);
+  uint32_t nbk = msk_block_excl_scan<true>(first, kNone, msk_op_min(), wtot, &all);
   const uint32_t cin = b[nb + blockIdx.x], cout = b[2 * nb + blockIdx.x];
   na = na > cin ? na : cin;
   nbk = nbk < cout ? nbk : cout;

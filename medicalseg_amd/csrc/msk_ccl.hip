@@ -492,14 +492,6 @@ ccl_relabel_k(int* __restrict__ lab, const int* __restrict__ map, long total) {
   }
 }
 
-inline int ew_blocks(long total, int num_cu) {
-  long b = (total + kThreads - 1) / kThreads;
-  const long cap = (long)num_cu * 16;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 inline int bits_for(long v) {   // bits needed to hold 0..v
   int b = 0;
   while (v > 0) {
@@ -550,7 +542,7 @@ int run_ccl(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w
   }
   {
     msk_launch_scope ls(ctx, "ccl_merge");
-    hipLaunchKernelGGL(ccl_merge_k, dim3(ew_blocks(T_, ctx->num_cu)), dim3(kThreads), 0, st, par, status, g, T_);
+    hipLaunchKernelGGL(ccl_merge_k, dim3(msk_ew_blocks(T_, ctx->num_cu)), dim3(kThreads), 0, st, par, status, g, T_);
     MSK_LAUNCH_CHECK(ctx);
   }
   {
@@ -584,7 +576,7 @@ int run_ccl(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w
     }
     MSK_LAUNCH_CHECK(ctx);
   }
-  const int nbr = ew_blocks(M, ctx->num_cu);
+  const int nbr = msk_ew_blocks(M, ctx->num_cu);
   {
     msk_launch_scope ls(ctx, "ccl_rank");
     hipLaunchKernelGGL(ccl_segstart_k, dim3(nbr), dim3(kThreads), 0, st, (const int*)in, (const int*)nroots, g.vv, seg);
@@ -597,7 +589,7 @@ int run_ccl(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w
   }
   {
     msk_launch_scope ls(ctx, "ccl_relabel");
-    hipLaunchKernelGGL(ccl_relabel_k, dim3(ew_blocks(T_, ctx->num_cu)), dim3(kThreads), 0, st, par, (const int*)sizes, T_);
+    hipLaunchKernelGGL(ccl_relabel_k, dim3(msk_ew_blocks(T_, ctx->num_cu)), dim3(kThreads), 0, st, par, (const int*)sizes, T_);
     MSK_LAUNCH_CHECK(ctx);
   }
   return 0;

@@ -293,47 +293,5 @@ void msk_prof_attached(msk_ctx* ctx, const msk_launch_events& ev, const char* ta
 static inline int msk_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long msk_voxels(const msk_tensor& t) { return (long)t.n * t.d * t.h * t.w; }
 
-// device helpers ------------------------------------------------------------
-// Dense voxel records of rq float4 quads (rq <= 8) between HBM and an LDS tile of 256 records with WHOLE-LINE accesses (round 4):
-// a thread-per-voxel kernel whose lane reads its own 80-byte record touches 40 lines per 1 KiB load instruction and ran at
-// 1-1.9 TB/s (the 20-class MRI head and its loss: pointwise_mid_k, loss_*_tpv_k); here consecutive lanes move consecutive
-// 16-byte quads and a thread then takes its record from LDS.  pitch = rq | 1 slots: 16 consecutive records sit on 16 distinct
-// 16-byte bank groups, so the per-record ds_read_b128 / ds_write_b128 are conflict-free.
-__device__ __forceinline__ void msk_tile_load(const float* __restrict__ src, int nquads, int rq, int pitch, float4* __restrict__ tile) {
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (int i = threadIdx.x; i < nquads; i += blockDim.x) {
-    const int v = i / rq, q = i - v * rq;
-    tile[v * pitch + q] = s4[i];
-  }
-}
-__device__ __forceinline__ void msk_tile_store(float* __restrict__ dst, int nquads, int rq, int pitch, const float4* __restrict__ tile, bool accumulate) {
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  for (int i = threadIdx.x; i < nquads; i += blockDim.x) {
-    const int v = i / rq, q = i - v * rq;
-    float4 r = tile[v * pitch + q];
-    if (accumulate) {
-      const float4 o = d4[i];
-      r.x += o.x; r.y += o.y; r.z += o.z; r.w += o.w;
-    }
-    d4[i] = r;
-  }
-}
-
-// splitmix64: the word of the counter RNGs (Dropout3D masks in msk_elementwise.hip, Gaussian noise in msk_intensity.hip)
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ float msk_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double msk_wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
+// device and launch helpers shared by the kernel files
+#include "msk_device.h"

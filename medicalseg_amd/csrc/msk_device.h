@@ -1,0 +1,317 @@
+// Device and launch helpers shared by the libmsegk translation units (gfx950 only); included by msk_common.h.  Whatever two
+// kernel files need alike is stated HERE once: the pieces with a bit-for-bit contract against a numpy statement under tests/
+// (the fixed-order float64 reduction: tests/clip_reference.py, tests/intensity_reference.py) above all.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "msegk.h"
+
+// ---- grid size and argument predicates (host) ----------------------------------------------------------------------------------
+// workgroups of 256 threads for a grid-stride kernel over `total` items: clamp(ceil(total / 256), 1, num_cu * per_cu)
+static inline int msk_ew_blocks(long total, int num_cu, int per_cu = 16) {
+  long b = (total + 255) / 256;
+  const long cap = (long)num_cu * per_cu;
+  if (b > cap) b = cap;
+  return (int)(b < 1 ? 1 : b);
+}
+
+static inline bool msk_well_formed(const msk_tensor& t) {   // a non-empty float tensor with ld >= c
+  return t.p != nullptr && (((uintptr_t)t.p) & 3) == 0 && t.n >= 1 && t.d >= 1 && t.h >= 1 && t.w >= 1 && t.c >= 1 && t.ld >= t.c;
+}
+static inline bool msk_quad_dense(const msk_tensor& t) { return t.ld == t.c && (((uintptr_t)t.p) & 15) == 0; }
+static inline bool msk_same_shape(const msk_tensor& a, const msk_tensor& b) {
+  return a.n == b.n && a.d == b.d && a.h == b.h && a.w == b.w && a.c == b.c;
+}
+static inline bool msk_below_2_31(int d, int h, int w) { return (long)d * h * w <= 0x7fffffffL; }
+static inline bool msk_bytes_disjoint(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 + abytes <= b0 || b0 + bbytes <= a0;
+}
+
+// ---- LDS tiles, the counter RNG's word, wavefront sums ---------------------------------------------------------------------------
+// Dense voxel records of rq float4 quads (rq <= 8) between HBM and an LDS tile of 256 records with WHOLE-LINE accesses (round 4):
+// a thread-per-voxel kernel whose lane reads its own 80-byte record touches 40 lines per 1 KiB load instruction and ran at
+// 1-1.9 TB/s (the 20-class MRI head and its loss: pointwise_mid_k, loss_*_tpv_k); here consecutive lanes move consecutive
+// 16-byte quads and a thread then takes its record from LDS.  pitch = rq | 1 slots: 16 consecutive records sit on 16 distinct
+// 16-byte bank groups, so the per-record ds_read_b128 / ds_write_b128 are conflict-free.
+__device__ __forceinline__ void msk_tile_load(const float* __restrict__ src, int nquads, int rq, int pitch, float4* __restrict__ tile) {
+  const float4* s4 = reinterpret_cast<const float4*>(src);
+  for (int i = threadIdx.x; i < nquads; i += blockDim.x) {
+    const int v = i / rq, q = i - v * rq;
+    tile[v * pitch + q] = s4[i];
+  }
+}
+__device__ __forceinline__ void msk_tile_store(float* __restrict__ dst, int nquads, int rq, int pitch, const float4* __restrict__ tile, bool accumulate) {
+  float4* d4 = reinterpret_cast<float4*>(dst);
+  for (int i = threadIdx.x; i < nquads; i += blockDim.x) {
+    const int v = i / rq, q = i - v * rq;
+    float4 r = tile[v * pitch + q];
+    if (accumulate) {
+      const float4 o = d4[i];
+      r.x += o.x; r.y += o.y; r.z += o.z; r.w += o.w;
+    }
+    d4[i] = r;
+  }
+}
+
+// splitmix64: the word of the counter RNGs (Dropout3D masks in msk_elementwise.hip, Gaussian noise in msk_intensity.hip)
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float msk_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double msk_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t msk_wave_sum_u32(uint32_t v) {   // the sum in every lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---- scans over a wavefront and a workgroup ----------------------------------------------------------------------------------------
+struct msk_op_add { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
+struct msk_op_max { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
+struct msk_op_min { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
+
+// Inclusive scan of one value per lane in lane order (REV: in reverse lane order, i.e. over the lanes behind this one).
+template <bool REV, class Op>
+__device__ __forceinline__ uint32_t msk_wave_incl_scan(uint32_t v, Op op) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int src = REV ? lane + o : lane - o;
+    const uint32_t t = __shfl(v, src & 63, 64);
+    if (src >= 0 && src < 64) v = op(v, t);
+  }
+  return v;
+}
+
+// Exclusive scan of one value per thread in thread order (REV: in reverse thread order, i.e. over the threads behind this
+// one); *total = the combination of all threads.  Called by every thread.  wtot: one LDS word per wavefront, reusable after the
+// call returns.
+template <bool REV, class Op>
+__device__ __forceinline__ uint32_t msk_block_excl_scan(uint32_t v, uint32_t identity, Op op, uint32_t* wtot, uint32_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const uint32_t inc = msk_wave_incl_scan<REV>(v, op);
+  const int nb = REV ? lane + 1 : lane - 1;
+  const uint32_t left = __shfl(inc, nb & 63, 64);
+  uint32_t ex = (nb >= 0 && nb < 64) ? left : identity;
+  __syncthreads();   // the previous use of wtot is over
+  if (lane == (REV ? 0 : 63)) wtot[wave] = inc;
+  __syncthreads();
+  uint32_t before = identity, all = identity;
+  for (int w = 0; w < nw; ++w) {
+    const uint32_t t = wtot[w];
+    all = op(all, t);
+    if (REV ? w > wave : w < wave) before = op(before, t);
+  }
+  *total = all;
+  return op(before, ex);
+}
+template <bool REV, class Op>
+__device__ __forceinline__ uint32_t msk_block_excl_scan(uint32_t v, uint32_t identity, Op op, uint32_t* wtot) {
+  uint32_t total;
+  return msk_block_excl_scan<REV>(v, identity, op, wtot, &total);
+}
+
+// ---- wave-aggregated LDS histogram add -------------------------------------------------------------------------------------------
+// A slot is one voxel per lane.  A label volume is mostly one class, so most slots hold one key 64 times, and 64 LDS atomics on one
+// address serialise.  msk_count_slot peels keys off the slot: it takes the key of the first remaining lane, ballots the lanes
+// that hold the same key and, when they are kMskPeelMin or more, adds their number with ONE single-lane LDS atomic.  Up to kMskPeel
+// keys are peeled; after kMskPeelMiss keys that were held by fewer than kMskPeelMin lanes the slot counts as "scattered" (many
+// classes, random data) and the remaining lanes add 1 each: such lanes share an address with at most a few others.
+constexpr int kMskPeel = 8;        // most keys peeled off one slot
+constexpr int kMskPeelMin = 4;     // a key held by fewer lanes is left to the per-lane adds (<= 3 adds on one address)
+constexpr int kMskPeelMiss = 2;    // such keys in one slot before the peeling stops
+
+// one voxel per lane, key < 0 = no voxel; called by every lane of the wavefront
+__device__ __forceinline__ void msk_count_slot(int key, uint32_t* __restrict__ hist, int lane) {
+  unsigned long long rest = __ballot(key >= 0);
+  unsigned long long single = 0;
+  int miss = 0;
+  for (int it = 0; it < kMskPeel && rest != 0 && miss < kMskPeelMiss; ++it) {
+    const int first = __ffsll((long long)rest) - 1;
+    const int k = __builtin_amdgcn_readlane(key, first);
+    const unsigned long long m = __ballot(key == k);   // a subset of rest: every lane of an earlier key has left it
+    const int c = __popcll(m);
+    if (c >= kMskPeelMin) {
+      if (lane == first) atomicAdd(&hist[k], (uint32_t)c);
+    } else {
+      single |= m;
+      ++miss;
+    }
+    rest &= ~m;
+  }
+  if (((rest | single) >> lane) & 1) atomicAdd(&hist[key], 1u);
+}
+
+// ---- the fixed-order float64 reduction ---------------------------------------------------------------------------------------------
+// sum of squares of n floats (STATS: also sum, min and max) with an order of additions that is part of the result: the numpy
+// statements reproduce it bit for bit.  Two passes:
+//   chunk   one WAVEFRONT per chunk of kMskRedChunk = 4096 elements.  The statement's lane l of 256 adds x[l], x[l+256], ... in
+//           float64; thread m of 64 carries the four lanes 4m .. 4m+3: its 16 loads are the quads 64j + m, j = 0..15, so every
+//           load instruction of the wavefront is 1 KiB of consecutive bytes and all 16 are issued before the first add.  The tree
+//           v[l] += v[l+s] is a xor butterfly over m for s = 128 .. 4 (a + b == b + a bit for bit) and two additions inside the
+//           thread for s = 2, 1.  min / max ride along.  A pointer that is only 4-byte aligned and the last, partial chunk take
+//           the same lanes one element at a time; elements past n add the statement's + 0.0 (it turns a -0.0 into +0.0).
+//   finish  one workgroup of 256 over the chunk values P: lane l adds P[l], P[l+256], ... in ascending order, eight loads in
+//           flight, then the LDS tree.
+// The files that instantiate these compile with different contraction settings (msk_intensity.hip rounds every multiply and add
+// on its own, msk_clip.hip does not).  Whichever setting reaches the bodies here, the bits are the same: (double)x * (double)x is
+// exact (48 bits of product), so a fused multiply-add rounds as a multiply and an add do, and nothing else below multiplies.
+constexpr int kMskRedChunk = 4096;   // elements per chunk
+constexpr int kMskRedLanes = 256;    // lanes of the statement = threads of the finish pass
+
+static inline long msk_chunks_of(size_t n) { return (long)((n + kMskRedChunk - 1) / kMskRedChunk); }
+
+__device__ __forceinline__ double msk_shfl_xor_d(double v, int mask) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __shfl_xor(lo, mask, 64);
+  hi = __shfl_xor(hi, mask, 64);
+  return __hiloint2double(hi, lo);
+}
+
+struct msk_red_vals {   // without STATS only sumsq means anything
+  double sum, sumsq;
+  float mn, mx;
+};
+
+// called by the 64 threads of workgroup blockIdx.x = chunk; vec: x is 16-byte aligned.  The chunk's values, in every thread.
+template <bool STATS>
+__device__ __forceinline__ msk_red_vals msk_red_chunk(const float* __restrict__ x, long n, bool vec) {
+  const int m = threadIdx.x;
+  const long base = (long)blockIdx.x * kMskRedChunk;
+  const long left = n - base;                       // >= 1
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+  float mn = INFINITY, mx = -INFINITY;
+  if (vec && left >= kMskRedChunk) {
+    const float4* x4 = reinterpret_cast<const float4*>(x + base);
+    float4 v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = x4[64 * j + m];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const double d = (double)e[i];
+        if (STATS) s[i] = s[i] + d;
+        q[i] = q[i] + d * d;
+        if (STATS) mn = fminf(mn, e[i]);
+        if (STATS) mx = fmaxf(mx, e[i]);
+      }
+    }
+  } else {
+    const float* xc = x + base;
+    for (int j = 0; j < 16; ++j) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long e = 256L * j + 4 * m + i;
+        if (e < left) {
+          const float f = xc[e];
+          const double d = (double)f;
+          if (STATS) s[i] = s[i] + d;
+          q[i] = q[i] + d * d;
+          if (STATS) mn = fminf(mn, f);
+          if (STATS) mx = fmaxf(mx, f);
+        } else {                                    // the statement's + 0.0
+          if (STATS) s[i] = s[i] + 0.0;
+          q[i] = q[i] + 0.0;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {                // s = 128 .. 4 of the tree
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (STATS) s[i] = s[i] + msk_shfl_xor_d(s[i], o);
+      q[i] = q[i] + msk_shfl_xor_d(q[i], o);
+    }
+    if (STATS) mn = fminf(mn, __shfl_xor(mn, o, 64));
+    if (STATS) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  }
+  msk_red_vals r;
+  r.sum = (s[0] + s[2]) + (s[1] + s[3]);            // s = 2, then s = 1
+  r.sumsq = (q[0] + q[2]) + (q[1] + q[3]);
+  r.mn = mn;
+  r.mx = mx;
+  return r;
+}
+
+// called by the one workgroup of kMskRedLanes threads over the nc chunk values (psum, pmn, pmx: read with STATS only).  The
+// values of the whole array, in every thread.
+template <bool STATS>
+__device__ __forceinline__ msk_red_vals msk_red_finish(long nc, const double* __restrict__ psum, const double* __restrict__ psq,
+                                                       const float* __restrict__ pmn, const float* __restrict__ pmx) {
+  constexpr int L = kMskRedLanes;
+  __shared__ double ts[STATS ? L : 1], tq[L];
+  __shared__ float tmn[STATS ? L : 1], tmx[STATS ? L : 1];
+  const int l = threadIdx.x;
+  double s = 0.0, q = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+  long c = l;
+  for (; c + 7L * L < nc; c += 8L * L) {            // eight loads in flight, added in order
+    double a[8], b[8];
+    float lo[8], hi[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      b[u] = psq[c + (long)u * L];
+      if (STATS) {
+        a[u] = psum[c + (long)u * L];
+        lo[u] = pmn[c + (long)u * L];
+        hi[u] = pmx[c + (long)u * L];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      q = q + b[u];
+      if (STATS) {
+        s = s + a[u];
+        mn = fminf(mn, lo[u]);
+        mx = fmaxf(mx, hi[u]);
+      }
+    }
+  }
+  for (; c < nc; c += L) {
+    q = q + psq[c];
+    if (STATS) {
+      s = s + psum[c];
+      mn = fminf(mn, pmn[c]);
+      mx = fmaxf(mx, pmx[c]);
+    }
+  }
+  tq[l] = q;
+  if (STATS) { ts[l] = s; tmn[l] = mn; tmx[l] = mx; }
+  __syncthreads();
+  for (int o = L / 2; o > 0; o >>= 1) {
+    if (l < o) {
+      tq[l] = tq[l] + tq[l + o];
+      if (STATS) {
+        ts[l] = ts[l] + ts[l + o];
+        tmn[l] = fminf(tmn[l], tmn[l + o]);
+        tmx[l] = fmaxf(tmx[l], tmx[l + o]);
+      }
+    }
+    __syncthreads();
+  }
+  msk_red_vals r;
+  r.sumsq = tq[0];
+  r.sum = STATS ? ts[0] : 0.0;
+  r.mn = STATS ? tmn[0] : 0.f;
+  r.mx = STATS ? tmx[0] : 0.f;
+  return r;
+}

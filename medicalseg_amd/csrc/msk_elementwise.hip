@@ -1218,17 +1218,6 @@ int g_dense12 = 1;   // option "dense12": 0 = the scalar kernels (A/B)
 inline bool vec4_ok(const msk_tensor& t) {
   return t.p == nullptr || ((t.c % 4 == 0) && (t.ld % 4 == 0) && (((uintptr_t)t.p) % 16 == 0));
 }
-inline int ew_blocks(long total, int num_cu) {
-  long b = (total + kThreads - 1) / kThreads;
-  long cap = (long)num_cu * g_ew_cap;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-inline bool same_shape(const msk_tensor& a, const msk_tensor& b) {
-  return a.n == b.n && a.d == b.d && a.h == b.h && a.w == b.w && a.c == b.c;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1364,7 +1353,7 @@ int msk_bn_eval_coeffs(msk_ctx* ctx, int C, const float* gamma, const float* bet
 static int affine_act_fwd_impl(msk_ctx* ctx, msk_tensor x, const float* scale, const float* shift, msk_tensor res,
                                const float* alpha, msk_tensor out, const float* alpha_in, float* out_amax = nullptr,
                                msk_tensor out2 = msk_tensor{}) {
-  MSK_REQUIRE(ctx, same_shape(x, out), "x/out shape mismatch");
+  MSK_REQUIRE(ctx, msk_same_shape(x, out), "x/out shape mismatch");
   MSK_REQUIRE(ctx, (scale == nullptr) == (shift == nullptr), "scale and shift go together");
   if (res.p) MSK_REQUIRE(ctx, res.c > 0 && (res.c == x.c || x.c % res.c == 0), "residual channels must tile");
   const long voxels = msk_voxels(x);
@@ -1373,7 +1362,7 @@ static int affine_act_fwd_impl(msk_ctx* ctx, msk_tensor x, const float* scale, c
   const int cq = x.c / 4;
   if (g_dense12 && !v4 && !alpha_in && !out2.p && d12_shape(x, voxels) && d12_ok(x) && d12_ok(out) && (res.p == nullptr || (res.c == x.c && d12_ok(res)))) {
     const long groups = voxels * x.c / 12;
-    const dim3 grid(ew_blocks(groups, ctx->num_cu));
+    const dim3 grid(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap));
 #define D12_FWD(C_) hipLaunchKernelGGL(affine_act_fwd_d12_k<C_>, grid, dim3(kThreads), 0, ctx->stream, (const float*)x.p, scale, shift, \
                                        (const float*)res.p, alpha, (float*)out.p, groups, (unsigned*)out_amax)
     if (x.c == 1) D12_FWD(1); else if (x.c == 2) D12_FWD(2); else if (x.c == 3) D12_FWD(3); else D12_FWD(6);
@@ -1384,7 +1373,7 @@ static int affine_act_fwd_impl(msk_ctx* ctx, msk_tensor x, const float* scale, c
   if (v4 && cq >= 1 && (cq & (cq - 1)) == 0 && cq <= kThreads) {
     int cshift = 0;
     while ((1 << cshift) < cq) ++cshift;
-    hipLaunchKernelGGL(affine_act_fwd_cs_k, dim3(ew_blocks(voxels * cq / 2, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(affine_act_fwd_cs_k, dim3(msk_ew_blocks(voxels * cq / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0, ctx->stream,
                        (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, (float*)out.p,
                        out.ld, voxels, x.c, cshift, alpha_in, (unsigned*)out_amax, (float*)out2.p, out2.ld);
     MSK_LAUNCH_CHECK(ctx);
@@ -1392,11 +1381,11 @@ static int affine_act_fwd_impl(msk_ctx* ctx, msk_tensor x, const float* scale, c
   } else if (out2.p) {
     return msk_fail(ctx, __FILE__, __LINE__, "msk_affine_act_fwd_amax2", "the second output needs the channel-stationary float4 kernel (C / 4 a power of two, aligned tensors)");
   } else if (v4) {
-    hipLaunchKernelGGL(affine_act_fwd_k<4>, dim3(ew_blocks(voxels * x.c / 4, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(affine_act_fwd_k<4>, dim3(msk_ew_blocks(voxels * x.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, (float*)out.p, out.ld, voxels, x.c, alpha_in, (unsigned*)out_amax);
   } else {
-    hipLaunchKernelGGL(affine_act_fwd_k<1>, dim3(ew_blocks(voxels * x.c, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(affine_act_fwd_k<1>, dim3(msk_ew_blocks(voxels * x.c, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, (float*)out.p, out.ld, voxels, x.c, alpha_in, (unsigned*)out_amax);
   }
@@ -1413,7 +1402,7 @@ int msk_affine_act_fwd_amax(msk_ctx* ctx, msk_tensor x, const float* scale, cons
 
 int msk_affine_act_fwd_amax2(msk_ctx* ctx, msk_tensor x, const float* scale, const float* shift, msk_tensor res,
                              const float* alpha, msk_tensor out, float* out_amax, msk_tensor out2) {
-  if (out2.p) MSK_REQUIRE(ctx, same_shape(x, out2) && vec4_ok(out2), "out2 must have x's shape and float4 alignment");
+  if (out2.p) MSK_REQUIRE(ctx, msk_same_shape(x, out2) && vec4_ok(out2), "out2 must have x's shape and float4 alignment");
   return affine_act_fwd_impl(ctx, x, scale, shift, res, alpha, out, nullptr, out_amax, out2);
 }
 
@@ -1451,7 +1440,7 @@ int msk_affine_act_bwd_reduce_ex(msk_ctx* ctx, msk_tensor x, const float* scale,
 int msk_affine_act_bwd_reduce_pg(msk_ctx* ctx, msk_tensor x, const float* scale, const float* shift, msk_tensor res,
                                  const float* alpha, const float* mean, const float* invstd, msk_tensor dout,
                                  float* sums, float* maxes, int clear_maxes, float* dgamma, float* dbeta, float* dalpha) {
-  MSK_REQUIRE(ctx, same_shape(x, dout), "x/dout shape mismatch");
+  MSK_REQUIRE(ctx, msk_same_shape(x, dout), "x/dout shape mismatch");
   const long voxels = msk_voxels(x);
   const bool v4 = x.c % 4 == 0 && x.c / 4 <= kThreads && vec4_ok(x) && vec4_ok(dout) &&
                   (res.p == nullptr || res.c != x.c || vec4_ok(res));
@@ -1531,9 +1520,9 @@ int msk_affine_act_bwd_apply_amax(msk_ctx* ctx, msk_tensor x, const float* scale
                                   msk_tensor dout, const float* sums_total, double M_total, int bn_mode,
                                   msk_tensor dx, msk_tensor dres, int dres_acc, float* dx_amax) {
   (void)gamma;
-  MSK_REQUIRE(ctx, same_shape(x, dout), "x/dout shape mismatch");
-  if (dx.p) MSK_REQUIRE(ctx, same_shape(x, dx), "x/dx shape mismatch");
-  if (dres.p) MSK_REQUIRE(ctx, same_shape(x, dres), "dres must have the full channel count");
+  MSK_REQUIRE(ctx, msk_same_shape(x, dout), "x/dout shape mismatch");
+  if (dx.p) MSK_REQUIRE(ctx, msk_same_shape(x, dx), "x/dx shape mismatch");
+  if (dres.p) MSK_REQUIRE(ctx, msk_same_shape(x, dres), "dres must have the full channel count");
   if (bn_mode == 1) MSK_REQUIRE(ctx, sums_total && mean && invstd && scale, "training BN backward needs sums/mean/invstd/scale");
   if (bn_mode == 2) MSK_REQUIRE(ctx, scale != nullptr, "eval BN backward needs scale");
   const long voxels = msk_voxels(x);
@@ -1545,7 +1534,7 @@ int msk_affine_act_bwd_apply_amax(msk_ctx* ctx, msk_tensor x, const float* scale
   if (g_dense12 && !v4 && d12_shape(x, voxels) && d12_ok(x) && d12_ok(dout) && d12_ok(dx) && d12_ok(dres) &&
       (res.p == nullptr || (res.c == x.c && d12_ok(res)))) {
     const long groups = voxels * x.c / 12;
-    const dim3 grid(ew_blocks(groups, ctx->num_cu));
+    const dim3 grid(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap));
 #define D12_AP(C_) hipLaunchKernelGGL(affine_act_bwd_apply_d12_k<C_>, grid, dim3(kThreads), 0, ctx->stream, (const float*)x.p, scale, shift, \
                                       (const float*)res.p, alpha, mean, invstd, (const float*)dout.p, sums_total, invM, bn_mode, (float*)dx.p, \
                                       (float*)dres.p, dres_acc, groups, x.c, (unsigned*)dx_amax)
@@ -1557,17 +1546,17 @@ int msk_affine_act_bwd_apply_amax(msk_ctx* ctx, msk_tensor x, const float* scale
   if (v4 && cq >= 1 && (cq & (cq - 1)) == 0 && cq <= kThreads) {
     int cshift = 0;
     while ((1 << cshift) < cq) ++cshift;
-    hipLaunchKernelGGL(affine_act_bwd_apply_cs_k, dim3(ew_blocks(voxels * cq / 2, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(affine_act_bwd_apply_cs_k, dim3(msk_ew_blocks(voxels * cq / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean,
                        invstd, (const float*)dout.p, dout.ld, sums_total, invM, bn_mode, (float*)dx.p, dx.ld,
                        (float*)dres.p, dres.ld, dres_acc, voxels, x.c, cshift, (unsigned*)dx_amax);
   } else if (v4) {
-    hipLaunchKernelGGL(affine_act_bwd_apply_k<4>, dim3(ew_blocks(voxels * x.c / 4, ctx->num_cu)), dim3(kThreads),
+    hipLaunchKernelGGL(affine_act_bwd_apply_k<4>, dim3(msk_ew_blocks(voxels * x.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads),
                        0, ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, mean, invstd, (const float*)dout.p, dout.ld, sums_total, invM, bn_mode,
                        (float*)dx.p, dx.ld, (float*)dres.p, dres.ld, dres_acc, voxels, x.c, (unsigned*)dx_amax);
   } else {
-    hipLaunchKernelGGL(affine_act_bwd_apply_k<1>, dim3(ew_blocks(voxels * x.c, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(affine_act_bwd_apply_k<1>, dim3(msk_ew_blocks(voxels * x.c, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, mean, invstd, (const float*)dout.p, dout.ld, sums_total, invM, bn_mode,
                        (float*)dx.p, dx.ld, (float*)dres.p, dres.ld, dres_acc, voxels, x.c, (unsigned*)dx_amax);
@@ -1583,7 +1572,7 @@ static int add_act_bwd_impl(msk_ctx* ctx, msk_tensor a, const float* scale, cons
                            float* u_dalpha = nullptr) {
   // db.p == null (round 6): the second operand's gradient is NOT written -- it equals da, and its consumer reads da instead
   // (msk_conv3d_bwd_bnact_acc's dx_old): one write of the tensor less per join
-  MSK_REQUIRE(ctx, same_shape(a, b) && same_shape(a, dout) && same_shape(a, da) && (!db.p || same_shape(a, db)), "shape mismatch");
+  MSK_REQUIRE(ctx, msk_same_shape(a, b) && msk_same_shape(a, dout) && msk_same_shape(a, da) && (!db.p || msk_same_shape(a, db)), "shape mismatch");
   MSK_REQUIRE(ctx, db.p || !db_accumulate, "a skipped second gradient cannot accumulate");
   MSK_REQUIRE(ctx, alpha != nullptr && dalpha != nullptr, "join needs alpha and its gradient");
   MSK_REQUIRE(ctx, a.c % 4 == 0 && a.c / 4 <= kThreads && vec4_ok(a) && vec4_ok(b) && vec4_ok(dout) && vec4_ok(da) &&
@@ -1681,16 +1670,16 @@ int msk_copy_scale(msk_ctx* ctx, msk_tensor src, const float* mask, msk_tensor d
 }
 
 int msk_copy_scale_amax(msk_ctx* ctx, msk_tensor src, const float* mask, msk_tensor dst, int accumulate, float* dst_amax) {
-  MSK_REQUIRE(ctx, same_shape(src, dst), "src/dst shape mismatch");
+  MSK_REQUIRE(ctx, msk_same_shape(src, dst), "src/dst shape mismatch");
   const long voxels = msk_voxels(src);
   const long vpn = (long)src.d * src.h * src.w;
   msk_launch_scope ls(ctx, "copy_scale");
   if (vec4_ok(src) && vec4_ok(dst)) {
-    hipLaunchKernelGGL(copy_scale_k<4>, dim3(ew_blocks(voxels * src.c / 4, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(copy_scale_k<4>, dim3(msk_ew_blocks(voxels * src.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)src.p, src.ld, mask, (float*)dst.p, dst.ld, voxels, vpn, src.c,
                        accumulate, (unsigned*)dst_amax);
   } else {
-    hipLaunchKernelGGL(copy_scale_k<1>, dim3(ew_blocks(voxels * src.c, ctx->num_cu)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(copy_scale_k<1>, dim3(msk_ew_blocks(voxels * src.c, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)src.p, src.ld, mask, (float*)dst.p, dst.ld, voxels, vpn, src.c,
                        accumulate, (unsigned*)dst_amax);
   }
@@ -1748,10 +1737,10 @@ int msk_channel_sum(msk_ctx* ctx, msk_tensor x, float* out, int accumulate) {
 }
 
 int msk_softmax_c(msk_ctx* ctx, msk_tensor x, msk_tensor out) {
-  MSK_REQUIRE(ctx, same_shape(x, out), "x/out shape mismatch");
+  MSK_REQUIRE(ctx, msk_same_shape(x, out), "x/out shape mismatch");
   const long voxels = msk_voxels(x);
   msk_launch_scope ls(ctx, "softmax_c");
-  hipLaunchKernelGGL(softmax_c_k, dim3(ew_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, (const float*)x.p, x.ld,
+  hipLaunchKernelGGL(softmax_c_k, dim3(msk_ew_blocks(voxels, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0, ctx->stream, (const float*)x.p, x.ld,
                      voxels, x.c, (float*)out.p, out.ld);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
@@ -1760,7 +1749,7 @@ int msk_softmax_c(msk_ctx* ctx, msk_tensor x, msk_tensor out) {
 int msk_argmax_c(msk_ctx* ctx, msk_tensor x, int32_t* out) {
   const long voxels = msk_voxels(x);
   msk_launch_scope ls(ctx, "argmax_c");
-  hipLaunchKernelGGL(argmax_k, dim3(ew_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+  hipLaunchKernelGGL(argmax_k, dim3(msk_ew_blocks(voxels, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0, ctx->stream,
                      (const float*)x.p, x.ld, voxels, x.c, out);
   MSK_LAUNCH_CHECK(ctx);
   return 0;

@@ -4,12 +4,9 @@
 // statistics a transform needs are read from a DEVICE record by the pass that uses them, so a whole transform is enqueued
 // without the host ever seeing a value.
 //
-//   stats   one WAVEFRONT per chunk of kChunk = 4096 voxels.  The statement's lane l of 256 adds x[l], x[l+256], ... in float64;
-//           here thread m of 64 carries the four lanes 4m .. 4m+3: its 16 loads are the quads 64j + m, j = 0..15, so every load
-//           instruction of the wavefront is 1 KiB of consecutive bytes and all 16 are issued together.  The tree v[l] += v[l+s]
-//           is a xor butterfly over m for s = 128 .. 4 (a + b == b + a bit for bit) and two additions inside the thread for
-//           s = 2, 1.  min / max ride along.  The chunk values go to the workspace (24 bytes per 16 KiB of volume); a second
-//           launch of one workgroup reduces them by the same scheme, 8 loads in flight per lane.
+//   stats   the fixed-order float64 reduction of msk_device.h (msk_red_chunk / msk_red_finish, the one msk_grad_clip_coef uses)
+//           with sum, min and max riding along: one wavefront per chunk of 4096 voxels, the chunk values go to the workspace
+//           (24 bytes per 16 KiB of volume), and a second launch of one workgroup reduces them.
 //   apply   a workgroup takes tiles of 1024 quads (four 16-byte loads per lane, issued together) in a grid-stride loop, so
 //           the scalars derived from the records (a float64 division, a square root) are computed once per thread and not
 //           once per quad; a scalar form for pointers that are only 4-byte aligned and for the last n % 4 elements.
@@ -25,138 +22,36 @@
 
 namespace {
 
-constexpr int kChunk = 4096;     // voxels per chunk of the statistics
-constexpr int kLanes = 256;      // lanes of the statement
 constexpr int kMaxR = 8;         // blur radius
 constexpr int kSeg = 16;         // outputs per thread of the column passes
 constexpr int kTile = 1024;      // outputs per workgroup of the W pass
 constexpr int kThreads = 256;
 
-inline long chunks_of(long n) { return (n + kChunk - 1) / kChunk; }
-
 // ---- statistics --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double shfl_xor_d(double v, int mask) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, mask, 64);
-  hi = __shfl_xor(hi, mask, 64);
-  return __hiloint2double(hi, lo);
-}
-
 // workspace: sum[nc], sumsq[nc] (double), mn[nc], mx[nc] (float)
 // grid: one wavefront (64 threads) per chunk
 __global__ void __launch_bounds__(64)
 intensity_chunk_k(const float* __restrict__ x, long n, int vec, long nc, double* __restrict__ psum, double* __restrict__ psq,
                   float* __restrict__ pmn, float* __restrict__ pmx) {
-  const int m = threadIdx.x;
-  const long base = (long)blockIdx.x * kChunk;
-  const long left = n - base;                       // >= 1
-  double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
-  float mn = INFINITY, mx = -INFINITY;
-  if (vec && left >= kChunk) {
-    const float4* x4 = reinterpret_cast<const float4*>(x + base);
-    float4 v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = x4[64 * j + m];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const float e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double d = (double)e[i];
-        s[i] = s[i] + d;
-        q[i] = q[i] + d * d;
-        mn = fminf(mn, e[i]);
-        mx = fmaxf(mx, e[i]);
-      }
-    }
-  } else {
-    const float* xc = x + base;
-    for (int j = 0; j < 16; ++j) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long e = 256L * j + 4 * m + i;
-        if (e < left) {
-          const float f = xc[e];
-          const double d = (double)f;
-          s[i] = s[i] + d;
-          q[i] = q[i] + d * d;
-          mn = fminf(mn, f);
-          mx = fmaxf(mx, f);
-        } else {                                    // the statement's + 0.0 (it turns a -0.0 into +0.0)
-          s[i] = s[i] + 0.0;
-          q[i] = q[i] + 0.0;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                // s = 128 .. 4 of the tree
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      s[i] = s[i] + shfl_xor_d(s[i], o);
-      q[i] = q[i] + shfl_xor_d(q[i], o);
-    }
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  }
-  if (m == 0) {
-    psum[blockIdx.x] = (s[0] + s[2]) + (s[1] + s[3]);   // s = 2, then s = 1
-    psq[blockIdx.x] = (q[0] + q[2]) + (q[1] + q[3]);
-    pmn[blockIdx.x] = mn;
-    pmx[blockIdx.x] = mx;
+  const msk_red_vals r = msk_red_chunk<true>(x, n, vec != 0);
+  if (threadIdx.x == 0) {
+    psum[blockIdx.x] = r.sum;
+    psq[blockIdx.x] = r.sumsq;
+    pmn[blockIdx.x] = r.mn;
+    pmx[blockIdx.x] = r.mx;
   }
 }
 
-// one workgroup of 256: lane l adds P[l], P[l+256], ... in ascending order, then the tree
-__global__ void __launch_bounds__(kLanes)
+// one workgroup of 256; thread 0 writes the record
+__global__ void __launch_bounds__(kMskRedLanes)
 intensity_finish_k(long nc, const double* __restrict__ psum, const double* __restrict__ psq, const float* __restrict__ pmn,
                    const float* __restrict__ pmx, double* __restrict__ stats) {
-  __shared__ double ts[kLanes], tq[kLanes];
-  __shared__ float tmn[kLanes], tmx[kLanes];
-  const int l = threadIdx.x;
-  double s = 0.0, q = 0.0;
-  float mn = INFINITY, mx = -INFINITY;
-  long c = l;
-  for (; c + 7L * kLanes < nc; c += 8L * kLanes) {   // eight loads in flight, added in order
-    double a[8], b[8];
-    float lo[8], hi[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = psum[c + (long)u * kLanes];
-      b[u] = psq[c + (long)u * kLanes];
-      lo[u] = pmn[c + (long)u * kLanes];
-      hi[u] = pmx[c + (long)u * kLanes];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      s = s + a[u];
-      q = q + b[u];
-      mn = fminf(mn, lo[u]);
-      mx = fmaxf(mx, hi[u]);
-    }
-  }
-  for (; c < nc; c += kLanes) {
-    s = s + psum[c];
-    q = q + psq[c];
-    mn = fminf(mn, pmn[c]);
-    mx = fmaxf(mx, pmx[c]);
-  }
-  ts[l] = s; tq[l] = q; tmn[l] = mn; tmx[l] = mx;
-  __syncthreads();
-  for (int o = kLanes / 2; o > 0; o >>= 1) {
-    if (l < o) {
-      ts[l] = ts[l] + ts[l + o];
-      tq[l] = tq[l] + tq[l + o];
-      tmn[l] = fminf(tmn[l], tmn[l + o]);
-      tmx[l] = fmaxf(tmx[l], tmx[l + o]);
-    }
-    __syncthreads();
-  }
-  if (l == 0) {
-    stats[0] = (double)tmn[0];
-    stats[1] = (double)tmx[0];
-    stats[2] = ts[0];
-    stats[3] = tq[0];
+  const msk_red_vals r = msk_red_finish<true>(nc, psum, psq, pmn, pmx);
+  if (threadIdx.x == 0) {
+    stats[0] = (double)r.mn;
+    stats[1] = (double)r.mx;
+    stats[2] = r.sum;
+    stats[3] = r.sumsq;
   }
 }
 
@@ -377,11 +272,6 @@ void launch_row(msk_ctx* ctx, const float* src, float* dst, long n, int W, const
     default: fn<8>(__VA_ARGS__); break;    \
   }
 
-inline bool overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + bytes && b0 < a0 + bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -389,7 +279,7 @@ extern "C" {
 int msk_intensity_stats_workspace(long n, size_t* bytes) {
   MSK_REQUIRE(nullptr, bytes != nullptr, "bytes must not be null");
   MSK_REQUIRE(nullptr, n >= 1 && n <= 0x7fffffffL, "n must be in [1, 2^31)");
-  *bytes = ((size_t)chunks_of(n) * 24 + 255) & ~(size_t)255;
+  *bytes = ((size_t)msk_chunks_of((size_t)n) * 24 + 255) & ~(size_t)255;
   return 0;
 }
 
@@ -399,7 +289,7 @@ int msk_intensity_stats(msk_ctx* ctx, const float* x, long n, void* workspace, d
   MSK_REQUIRE(ctx, n >= 1 && n <= 0x7fffffffL, "n must be in [1, 2^31)");
   MSK_REQUIRE(ctx, (((uintptr_t)x) & 3) == 0, "x must be 4-byte aligned");
   MSK_REQUIRE(ctx, ((((uintptr_t)workspace) | ((uintptr_t)stats)) & 7) == 0, "workspace / stats must be 8-byte aligned");
-  const long nc = chunks_of(n);
+  const long nc = msk_chunks_of((size_t)n);
   double* psum = (double*)workspace;
   double* psq = psum + nc;
   float* pmn = (float*)(psq + nc);
@@ -411,7 +301,7 @@ int msk_intensity_stats(msk_ctx* ctx, const float* x, long n, void* workspace, d
   }
   {
     msk_launch_scope ls(ctx, "intensity_stats_finish");
-    hipLaunchKernelGGL(intensity_finish_k, dim3(1), dim3(kLanes), 0, ctx->stream, nc, (const double*)psum, (const double*)psq,
+    hipLaunchKernelGGL(intensity_finish_k, dim3(1), dim3(kMskRedLanes), 0, ctx->stream, nc, (const double*)psum, (const double*)psq,
                        (const float*)pmn, (const float*)pmx, stats);
   }
   MSK_LAUNCH_CHECK(ctx);
@@ -428,7 +318,7 @@ int msk_intensity_apply(msk_ctx* ctx, const float* x, float* y, long n, int mode
   MSK_REQUIRE(ctx, mode >= MSK_INTENSITY_NOISE && mode <= MSK_INTENSITY_RESTORE, "mode must be one of MSK_INTENSITY_*");
   MSK_REQUIRE(ctx, mode < MSK_INTENSITY_CONTRAST || stats_a != nullptr, "this mode needs stats_a");
   MSK_REQUIRE(ctx, mode != MSK_INTENSITY_RESTORE || stats_b != nullptr, "RESTORE needs stats_b");
-  MSK_REQUIRE(ctx, (const float*)y == x || !overlap(x, y, (size_t)n * 4), "y must be x or not overlap it");
+  MSK_REQUIRE(ctx, (const float*)y == x || msk_bytes_disjoint(x, (size_t)n * 4, y, (size_t)n * 4), "y must be x or not overlap it");
   ApplyArgs g;
   for (int i = 0; i < 4; ++i) g.p[i] = params[i];
   g.n = n;
@@ -457,11 +347,11 @@ int msk_gauss_blur3d(msk_ctx* ctx, const float* x, float* y, int d, int h, int w
   MSK_REQUIRE(ctx, ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)tmp)) & 3) == 0, "x / y / tmp must be 4-byte aligned");
   const long n = (long)d * h * w;
   const size_t bytes = (size_t)n * 4;
-  MSK_REQUIRE(ctx, !overlap(x, y, bytes), "y must not overlap x");
+  MSK_REQUIRE(ctx, msk_bytes_disjoint(x, bytes, y, bytes), "y must not overlap x");
   const int passes = (r_d > 0) + (r_h > 0) + (r_w > 0);
   if (passes >= 2) {
     MSK_REQUIRE(ctx, tmp != nullptr, "two or three blurred axes need tmp");
-    MSK_REQUIRE(ctx, !overlap(tmp, x, bytes) && !overlap(tmp, y, bytes), "tmp must overlap neither x nor y");
+    MSK_REQUIRE(ctx, msk_bytes_disjoint(tmp, bytes, x, bytes) && msk_bytes_disjoint(tmp, bytes, y, bytes), "tmp must overlap neither x nor y");
   }
   if (passes == 0) {
     MSK_CHECK_HIP(ctx, hipMemcpyAsync(y, x, bytes, hipMemcpyDeviceToDevice, ctx->stream));

@@ -117,13 +117,6 @@ interp_axis_bwd_k(const float* __restrict__ g, int gld, float* __restrict__ out,
   }
 }
 
-inline int blocks_for(long total, int num_cu) {
-  long b = (total + kThreads - 1) / kThreads;
-  const long cap = (long)num_cu * 16;
-  if (b > cap) b = cap;
-  return (int)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 extern "C" {
@@ -136,11 +129,11 @@ int msk_interp_trilinear_fwd(msk_ctx* ctx, msk_tensor src, msk_tensor dst) {
   const long total = msk_voxels(dst) * dst.c / (v4 ? 4 : 1);
   msk_launch_scope ls(ctx, "interp_trilinear_fwd");
   if (v4)
-    hipLaunchKernelGGL(interp_fwd_k<4>, dim3(blocks_for(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(interp_fwd_k<4>, dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                        (const float*)src.p, src.ld, src.d, src.h, src.w, (float*)dst.p, dst.ld, dst.d, dst.h, dst.w, dst.c,
                        total, (float)src.d / dst.d, (float)src.h / dst.h, (float)src.w / dst.w);
   else
-    hipLaunchKernelGGL(interp_fwd_k<1>, dim3(blocks_for(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(interp_fwd_k<1>, dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                        (const float*)src.p, src.ld, src.d, src.h, src.w, (float*)dst.p, dst.ld, dst.d, dst.h, dst.w, dst.c,
                        total, (float)src.d / dst.d, (float)src.h / dst.h, (float)src.w / dst.w);
   MSK_LAUNCH_CHECK(ctx);
@@ -181,21 +174,21 @@ int msk_interp_trilinear_bwd(msk_ctx* ctx, msk_tensor ddst, msk_tensor dsrc, int
   msk_launch_scope ls(ctx, "interp_trilinear_bwd");
   if (rw) {  // [N*Dd*Hd][Wd][1][C] -> [N*Dd*Hd][Ws][1][C]
     const long total = (long)ddst.n * ddst.d * ddst.h * dsrc.w * C / VV;
-    MSK_AXIS_BWD(dim3(blocks_for(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, t1, C, total, ddst.w, dsrc.w,
+    MSK_AXIS_BWD(dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, t1, C, total, ddst.w, dsrc.w,
                  1L, C, (float)dsrc.w / ddst.w, 0);
     MSK_LAUNCH_CHECK(ctx);
     cur = t1; cur_ld = C; cur_w = dsrc.w;
   }
   if (rh) {  // [N*Dd][Hd][W][C] -> [N*Dd][Hs][W][C]
     const long total = (long)ddst.n * ddst.d * dsrc.h * cur_w * C / VV;
-    MSK_AXIS_BWD(dim3(blocks_for(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, t2, C, total, ddst.h, dsrc.h,
+    MSK_AXIS_BWD(dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, t2, C, total, ddst.h, dsrc.h,
                  (long)cur_w, C, (float)dsrc.h / ddst.h, 0);
     MSK_LAUNCH_CHECK(ctx);
     cur = t2; cur_ld = C; cur_h = dsrc.h;
   }
   {  // [N][Dd][H*W][C] -> [N][Ds][H*W][C] (identity map when Dd == Ds)
     const long total = (long)ddst.n * dsrc.d * cur_h * cur_w * C / VV;
-    MSK_AXIS_BWD(dim3(blocks_for(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, (float*)dsrc.p, dsrc.ld, total,
+    MSK_AXIS_BWD(dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, cur, cur_ld, (float*)dsrc.p, dsrc.ld, total,
                  ddst.d, dsrc.d, (long)cur_h * cur_w, C, (float)dsrc.d / ddst.d, accumulate);
     MSK_LAUNCH_CHECK(ctx);
   }

@@ -6,13 +6,9 @@
 // two int32 streams; counts are integers, so the result is exact and does not depend on the order of the adds.
 //
 // Aggregation (three levels, integer atomics only):
-//   wavefront: a slot is one voxel per lane.  A label volume is 90-99 % background, so most slots hold one key 64
-//     times, and 64 LDS atomics on one address serialise.  count_slot therefore peels keys off the slot: it takes the
-//     key of the first remaining lane, ballots the lanes that hold the same key and, when they are kPeelMin or more,
-//     adds their number with ONE single-lane LDS atomic.  Up to kPeel keys are peeled; after kPeelMiss keys that were
-//     held by fewer than kPeelMin lanes the slot counts as "scattered" (many classes, random data) and the remaining
-//     lanes add 1 each: such lanes share an address with at most a few others.  One bin: 1 round and no per-lane
-//     atomic; 5 % foreground blobs: 1-2 rounds; 441 uniformly random bins: 2 short rounds + the per-lane adds.
+//   wavefront: a slot is one voxel per lane, and msk_count_slot (msk_device.h) adds a slot to the LDS histogram with one
+//     atomic per run of equal keys.  One bin: 1 round and no per-lane atomic; 5 % foreground blobs: 1-2 rounds; 441 uniformly
+//     random bins: 2 short rounds + the per-lane adds.
 //   workgroup: a 32-bit histogram in LDS (a workgroup sees far fewer than 2^32 voxels);
 //   grid: one 64-bit global atomic per non-zero bin per workgroup.
 //
@@ -24,36 +20,12 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPeel = 8;        // most keys peeled off one slot
-constexpr int kPeelMin = 4;     // a key held by fewer lanes is left to the per-lane adds (<= 3 adds on one address)
-constexpr int kPeelMiss = 2;    // such keys in one slot before the peeling stops
 constexpr long kBlockVoxels = 8192;   // least voxels per workgroup: bounds the global atomics (B per workgroup) of a small volume
 
 __device__ __forceinline__ int conf_key(int lab, int prd, int C, int K, int ignore_index) {
   const int r = (unsigned)lab < (unsigned)C ? lab : C;
   const int c = (unsigned)prd < (unsigned)C ? prd : C;
   return lab == ignore_index ? K * K : r * K + c;
-}
-
-// one voxel per lane, key < 0 = no voxel; called by every lane of the wavefront
-__device__ __forceinline__ void count_slot(int key, uint32_t* __restrict__ hist, int lane) {
-  unsigned long long rest = __ballot(key >= 0);
-  unsigned long long single = 0;
-  int miss = 0;
-  for (int it = 0; it < kPeel && rest != 0 && miss < kPeelMiss; ++it) {
-    const int first = __ffsll((long long)rest) - 1;
-    const int k = __builtin_amdgcn_readlane(key, first);
-    const unsigned long long m = __ballot(key == k);   // a subset of rest: every lane of an earlier key has left it
-    const int c = __popcll(m);
-    if (c >= kPeelMin) {
-      if (lane == first) atomicAdd(&hist[k], (uint32_t)c);
-    } else {
-      single |= m;
-      ++miss;
-    }
-    rest &= ~m;
-  }
-  if (((rest | single) >> lane) & 1) atomicAdd(&hist[key], 1u);
 }
 
 // elements [a, b) of one volume, one per lane, strided over the volume's workgroups
@@ -63,7 +35,7 @@ __device__ __forceinline__ void count_range(const int32_t* __restrict__ prd, con
   for (long i0 = a + (long)blockIdx.x * kThreads + (threadIdx.x & ~63); i0 < b; i0 += stride) {   // i0: the same in every lane
     const long i = i0 + lane;
     const int key = i < b ? conf_key(lab[i], prd[i], C, K, ignore_index) : -1;
-    count_slot(key, hist, lane);
+    msk_count_slot(key, hist, lane);
   }
 }
 
@@ -93,15 +65,15 @@ confusion_k(const int32_t* __restrict__ pred, const int32_t* __restrict__ label,
     const long ia = va ? qa : q0, ib = vb ? qb : q0;
     const int4 pa = p4[ia], la = l4[ia], pb = p4[ib], lb = l4[ib];
     const int ma = va ? 0 : -1, mb = vb ? 0 : -1;   // or-ed into the keys: -1 = no voxel
-    count_slot(conf_key(la.x, pa.x, C, K, ignore_index) | ma, hist, lane);
-    count_slot(conf_key(la.y, pa.y, C, K, ignore_index) | ma, hist, lane);
-    count_slot(conf_key(la.z, pa.z, C, K, ignore_index) | ma, hist, lane);
-    count_slot(conf_key(la.w, pa.w, C, K, ignore_index) | ma, hist, lane);
+    msk_count_slot(conf_key(la.x, pa.x, C, K, ignore_index) | ma, hist, lane);
+    msk_count_slot(conf_key(la.y, pa.y, C, K, ignore_index) | ma, hist, lane);
+    msk_count_slot(conf_key(la.z, pa.z, C, K, ignore_index) | ma, hist, lane);
+    msk_count_slot(conf_key(la.w, pa.w, C, K, ignore_index) | ma, hist, lane);
     if (q0 + stride < nvec) {   // the same in every lane
-      count_slot(conf_key(lb.x, pb.x, C, K, ignore_index) | mb, hist, lane);
-      count_slot(conf_key(lb.y, pb.y, C, K, ignore_index) | mb, hist, lane);
-      count_slot(conf_key(lb.z, pb.z, C, K, ignore_index) | mb, hist, lane);
-      count_slot(conf_key(lb.w, pb.w, C, K, ignore_index) | mb, hist, lane);
+      msk_count_slot(conf_key(lb.x, pb.x, C, K, ignore_index) | mb, hist, lane);
+      msk_count_slot(conf_key(lb.y, pb.y, C, K, ignore_index) | mb, hist, lane);
+      msk_count_slot(conf_key(lb.z, pb.z, C, K, ignore_index) | mb, hist, lane);
+      msk_count_slot(conf_key(lb.w, pb.w, C, K, ignore_index) | mb, hist, lane);
     }
   }
   count_range(prd, lab, 0, head, stride, C, K, ignore_index, hist, lane);

@@ -8,7 +8,7 @@
 //              scalar tail, and the scalar form for a label that is not 16-byte aligned).  Counts go into a 256-word LDS
 //              histogram.  A label volume is mostly one class, so a wavefront first asks whether its 256 voxels of one load
 //              hold ONE value and then adds 256 with a single LDS atomic; otherwise the four slots take the run-peeling of
-//              msk_metrics.hip's count_slot (repeated here: that one is private to its file).  The workgroup writes its row of C
+//              msk_count_slot (msk_device.h, shared with msk_metrics.hip).  The workgroup writes its row of C
 //              counters to the chunk table and adds its non-zero counters to the totals, one global atomic each.  The label
 //              is read once; the table is C / 4096 of its size.
 //   select     one workgroup per patch.  Class and rank follow from the totals and the patch's random words.  The class's
@@ -35,33 +35,11 @@ constexpr int kMaxSeg = 8192;                     // 2^31 voxels / kChunk / kSeg
 constexpr int kMaxClasses = 32;                   // candidate classes
 constexpr int kMaxPatches = 16;
 constexpr int kMaxNumClasses = 256;               // words of the LDS histogram == kThreads
-constexpr int kPeel = 8, kPeelMin = 4, kPeelMiss = 2;   // msk_metrics.hip
 
 static_assert(kMaxNumClasses == kThreads, "one lane per histogram word");
 static_assert((long)kMaxSeg * kSeg * kChunk >= (1L << 31), "segment sums for every volume below 2^31 voxels");
 
 __device__ __forceinline__ int class_key(int v, int C) { return (unsigned)v < (unsigned)C ? v : -1; }
-
-// one voxel per lane, key < 0 = nothing to count; called by every lane of the wavefront (msk_metrics.hip count_slot)
-__device__ __forceinline__ void count_slot(int key, uint32_t* __restrict__ hist, int lane) {
-  unsigned long long rest = __ballot(key >= 0);
-  unsigned long long single = 0;
-  int miss = 0;
-  for (int it = 0; it < kPeel && rest != 0 && miss < kPeelMiss; ++it) {
-    const int first = __ffsll((long long)rest) - 1;
-    const int k = __builtin_amdgcn_readlane(key, first);
-    const unsigned long long m = __ballot(key == k);
-    const int c = __popcll(m);
-    if (c >= kPeelMin) {
-      if (lane == first) atomicAdd(&hist[k], (uint32_t)c);
-    } else {
-      single |= m;
-      ++miss;
-    }
-    rest &= ~m;
-  }
-  if (((rest | single) >> lane) & 1) atomicAdd(&hist[key], 1u);
-}
 
 // grid: one workgroup per chunk.  table: [chunks][C], totals: [C] (zeroed before the launch)
 __global__ void __launch_bounds__(kThreads)
@@ -93,16 +71,16 @@ patch_hist_k(const int32_t* __restrict__ label, long V, int C, int vec, uint32_t
       if (__all(kx == k0 && ky == k0 && kz == k0 && kw == k0)) {   // 256 voxels of one value: one atomic, or none
         if (k0 >= 0 && lane == 0) atomicAdd(&hist[k0], 256u);
       } else {
-        count_slot(kx, hist, lane);
-        count_slot(ky, hist, lane);
-        count_slot(kz, hist, lane);
-        count_slot(kw, hist, lane);
+        msk_count_slot(kx, hist, lane);
+        msk_count_slot(ky, hist, lane);
+        msk_count_slot(kz, hist, lane);
+        msk_count_slot(kw, hist, lane);
       }
     }
   }
   for (int i0 = 4 * nvec + (t & ~63); i0 < n; i0 += kThreads) {   // i0: the same in every lane
     const int i = i0 + lane;
-    count_slot(i < n ? class_key(lab[i], C) : -1, hist, lane);
+    msk_count_slot(i < n ? class_key(lab[i], C) : -1, hist, lane);
   }
   __syncthreads();
   if (t < C) {
@@ -121,31 +99,6 @@ struct PatchSelArgs {
   int classes[kMaxClasses];
   uint32_t words[kMaxPatches * 6];
 };
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// exclusive prefix of v over the workgroup's threads in thread order; called by every thread; wsum: kThreads / 64 words of LDS
-__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* __restrict__ wsum) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan_u32(v, lane);
-  __syncthreads();   // the last call's readers are done with wsum
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t off = 0;
-  for (int k = 0; k < wave; ++k) off += wsum[k];
-  return off + incl - v;
-}
 
 __device__ __forceinline__ int pad_origin(int roi, int dim) { return -((roi - dim) / 2); }   // dim <= roi
 __device__ __forceinline__ int centred_origin(int c, int roi, int dim) {
@@ -204,7 +157,7 @@ patch_select_k(const int32_t* __restrict__ label, const PatchSelArgs a, const ui
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const uint32_t s = wave_sum_u32(v[u]);
+        const uint32_t s = msk_wave_sum_u32(v[u]);
         if (lane == 0 && s0 + u < nseg) segsum[s0 + u] = s;
       }
     }
@@ -214,7 +167,7 @@ patch_select_k(const int32_t* __restrict__ label, const PatchSelArgs a, const ui
     const int lo = t * G < nseg ? t * G : nseg, hi = lo + G < nseg ? lo + G : nseg;
     uint32_t mine = 0;
     for (int s = lo; s < hi; ++s) mine += segsum[s];
-    uint32_t excl = block_excl_scan_u32(mine, wsum);
+    uint32_t excl = msk_block_excl_scan<false>(mine, 0u, msk_op_add(), wsum);
     if (r >= excl && r - excl < mine) {
       uint32_t rr = r - excl;
       int s = lo;
@@ -228,7 +181,7 @@ patch_select_k(const int32_t* __restrict__ label, const PatchSelArgs a, const ui
     // the chunk: every wavefront scans the segment's counters (the same result in each)
     const long ch = (long)seg * kSeg + lane;
     const uint32_t cv = ch < a.nchunks ? table[ch * C + cls] : 0u;
-    const uint32_t cincl = wave_incl_scan_u32(cv, lane);
+    const uint32_t cincl = msk_wave_incl_scan<false>(cv, msk_op_add());
     const unsigned long long hit = __ballot(rr >= cincl - cv && rr < cincl);
     const int hl = hit ? __ffsll((long long)hit) - 1 : 0;
     long chunk = (long)seg * kSeg + hl;
@@ -253,7 +206,7 @@ patch_select_k(const int32_t* __restrict__ label, const PatchSelArgs a, const ui
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < kLaneVoxels; ++k) c += vals[k] == cls;
-    excl = block_excl_scan_u32(c, wsum);
+    excl = msk_block_excl_scan<false>(c, 0u, msk_op_add(), wsum);
     if (r2 >= excl && r2 - excl < c) {
       const uint32_t want = r2 - excl;
       uint32_t seen = 0;
@@ -336,7 +289,6 @@ patch_crop_elem_k(const uint32_t* __restrict__ src, const int32_t* __restrict__ 
 
 inline long chunks_of(long voxels) { return (voxels + kChunk - 1) / kChunk; }
 inline bool extents_ok(int d, int h, int w) { return d >= 1 && h >= 1 && w >= 1; }
-inline bool below_2_31(int d, int h, int w) { return (long)d * h * w <= 0x7fffffffL; }
 
 }  // namespace
 
@@ -359,7 +311,7 @@ int msk_patch_select(msk_ctx* ctx, const int32_t* label, int d, int h, int w, in
   MSK_REQUIRE(ctx, ((((uintptr_t)label) | ((uintptr_t)workspace) | ((uintptr_t)sel) | ((uintptr_t)counts)) & 3) == 0,
               "label / workspace / sel / counts must be 4-byte aligned");
   MSK_REQUIRE(ctx, extents_ok(d, h, w) && extents_ok(rd, rh, rw), "volume and patch extents must be >= 1");
-  MSK_REQUIRE(ctx, below_2_31(d, h, w), "the volume must have fewer than 2^31 voxels");
+  MSK_REQUIRE(ctx, msk_below_2_31(d, h, w), "the volume must have fewer than 2^31 voxels");
   MSK_REQUIRE(ctx, num_classes >= 1 && num_classes <= kMaxNumClasses, "num_classes must be in [1, 256]");
   MSK_REQUIRE(ctx, n_classes >= 0 && n_classes <= kMaxClasses, "n_classes must be in [0, 32]");
   MSK_REQUIRE(ctx, n_classes == 0 || classes != nullptr, "classes must be a host array of n_classes int32");
@@ -404,7 +356,7 @@ int msk_patch_crop(msk_ctx* ctx, const void* src, int d, int h, int w, const int
   MSK_REQUIRE(ctx, src != nullptr && sel != nullptr && dst != nullptr, "null src / sel / dst");
   MSK_REQUIRE(ctx, ((((uintptr_t)src) | ((uintptr_t)sel) | ((uintptr_t)dst)) & 3) == 0, "src / sel / dst must be 4-byte aligned");
   MSK_REQUIRE(ctx, extents_ok(d, h, w) && extents_ok(rd, rh, rw), "volume and patch extents must be >= 1");
-  MSK_REQUIRE(ctx, below_2_31(d, h, w) && below_2_31(rd, rh, rw), "volume and patch must have fewer than 2^31 voxels each");
+  MSK_REQUIRE(ctx, msk_below_2_31(d, h, w) && msk_below_2_31(rd, rh, rw), "volume and patch must have fewer than 2^31 voxels each");
   const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)d * h * w * 4, d0 = (uintptr_t)dst, d1 = d0 + (size_t)rd * rh * rw * 4;
   MSK_REQUIRE(ctx, s1 <= d0 || d1 <= s0, "dst must not overlap src");
   CropDims g;

@@ -10,14 +10,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-inline int ew_blocks(size_t total, int num_cu) {
-  size_t b = (total + kThreads - 1) / kThreads;
-  size_t cap = (size_t)num_cu * 16;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // coordinate of output index o along an axis: o * (n_in-1)/(n_out-1)  
 __device__ __forceinline__ double axis_coord(int o, int n_in, int n_out) {
   return n_out > 1 ? (double)o * ((double)(n_in - 1) / (double)(n_out - 1)) : 0.0;
@@ -221,7 +213,7 @@ static int crop_resample(msk_ctx* ctx, const void* src, int fd, int fh, int fw, 
   MSK_REQUIRE(ctx, ci >= 0 && cj >= 0 && ck >= 0 && ci + sd <= fd && cj + sh <= fh && ck + sw <= fw,
               "crop box outside the volume");
   const size_t total = (size_t)dd * dh * dw;
-  const int nb = ew_blocks(total, ctx->num_cu);
+  const int nb = msk_ew_blocks(total, ctx->num_cu);
   msk_launch_scope ls(ctx, order == 0 ? "resample3d_order0" : "resample3d_order1");
   if (dtype == 0) {
     if (order == 0)
@@ -256,7 +248,7 @@ int msk_flip3d(msk_ctx* ctx, const void* src, void* dst, int d, int h, int w, in
   if (total == 0) return 0;
   msk_launch_scope ls(ctx, "flip3d");
   // float32 and int32 are both 4-byte moves
-  hipLaunchKernelGGL((flip3d_k<uint32_t>), dim3(ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+  hipLaunchKernelGGL((flip3d_k<uint32_t>), dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                      (const uint32_t*)src, (uint32_t*)dst, d, h, w, axis);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
@@ -289,7 +281,7 @@ int msk_rotate3d(msk_ctx* ctx, const void* src, void* dst, int d, int h, int w, 
   const double m00 = c, m01 = s, m10 = -s, m11 = c;
   const double s0 = c0 - (m00 * c0 + m01 * c1), s1 = c1 - (m10 * c0 + m11 * c1);
   const size_t total = (size_t)d * h * w;
-  const int nb = ew_blocks(total, ctx->num_cu);
+  const int nb = msk_ew_blocks(total, ctx->num_cu);
   msk_launch_scope ls(ctx, "rotate3d");
   if (dtype == 0) {
     if (order == 0)
@@ -310,13 +302,13 @@ int msk_hu_norm(msk_ctx* ctx, const float* src, float* dst, size_t count, float 
   if (count == 0) return 0;
   const float scale = (float)(((double)hu_max - (double)hu_min) / 255.0);
   msk_launch_scope ls(ctx, "hu_norm");
-  hipLaunchKernelGGL(hu_norm_k, dim3(ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, hu_min, scale, hu_nan);
+  hipLaunchKernelGGL(hu_norm_k, dim3(msk_ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, hu_min, scale, hu_nan);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }
 
 static int minmax(msk_ctx* ctx, const float* src, size_t count, float** mm) {
-  int nb = ew_blocks(count, ctx->num_cu);
+  int nb = msk_ew_blocks(count, ctx->num_cu);
   if (nb > 1024) nb = 1024;
   float* partial = (float*)msk_workspace(ctx, (size_t)nb * 2 * sizeof(float));
   if (!partial) return -1;
@@ -341,7 +333,7 @@ int msk_minmax_norm(msk_ctx* ctx, const float* src, float* dst, size_t count, in
     if (minmax(ctx, src, count, &mm) != 0) return -1;
   }
   msk_launch_scope ls(ctx, "minmax_norm");
-  hipLaunchKernelGGL(norm_apply_k, dim3(ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, (const float*)mm, min_val, max_val, 0);
+  hipLaunchKernelGGL(norm_apply_k, dim3(msk_ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, (const float*)mm, min_val, max_val, 0);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -351,7 +343,7 @@ int msk_max_norm(msk_ctx* ctx, const float* src, float* dst, size_t count) {
   float* mm = nullptr;
   if (minmax(ctx, src, count, &mm) != 0) return -1;
   msk_launch_scope ls(ctx, "max_norm");
-  hipLaunchKernelGGL(norm_apply_k, dim3(ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, (const float*)mm, 0.f, 0.f, 1);
+  hipLaunchKernelGGL(norm_apply_k, dim3(msk_ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, src, dst, count, (const float*)mm, 0.f, 0.f, 1);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -359,7 +351,7 @@ int msk_max_norm(msk_ctx* ctx, const float* src, float* dst, size_t count) {
 int msk_label_remap(msk_ctx* ctx, int32_t* label, size_t count, const int32_t* keys, const int32_t* vals, int npairs) {
   if (count == 0 || npairs == 0) return 0;
   msk_launch_scope ls(ctx, "label_remap");
-  hipLaunchKernelGGL(label_remap_k, dim3(ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, label, count, keys, vals, npairs);
+  hipLaunchKernelGGL(label_remap_k, dim3(msk_ew_blocks(count, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, label, count, keys, vals, npairs);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }

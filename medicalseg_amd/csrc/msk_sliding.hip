@@ -139,10 +139,6 @@ sw_acc_elem_k(const float* __restrict__ logits, int lld, float* __restrict__ acc
   acc[ao] = rn_add(acc[ao], rn_mul(w, logits[lo]));
 }
 
-inline bool well_formed(const msk_tensor& t) {
-  return t.p != nullptr && (((uintptr_t)t.p) & 3) == 0 && t.n >= 1 && t.d >= 1 && t.h >= 1 && t.w >= 1 && t.c >= 1 && t.ld >= t.c;
-}
-inline bool quad_dense(const msk_tensor& t) { return t.ld == t.c && (((uintptr_t)t.p) & 15) == 0; }
 inline bool disjoint(const msk_tensor& a, const msk_tensor& b) {
   const uintptr_t a0 = (uintptr_t)a.p, a1 = a0 + ((size_t)(msk_voxels(a) - 1) * a.ld + a.c) * sizeof(float);
   const uintptr_t b0 = (uintptr_t)b.p, b1 = b0 + ((size_t)(msk_voxels(b) - 1) * b.ld + b.c) * sizeof(float);
@@ -184,14 +180,14 @@ inline long blocks_for(long total) { return (total + kThreads - 1) / kThreads; }
 extern "C" {
 
 int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_t* origins, float cval) {
-  MSK_REQUIRE(ctx, well_formed(vol) && well_formed(patches), "vol/patches must be non-empty float tensors with ld >= c");
+  MSK_REQUIRE(ctx, msk_well_formed(vol) && msk_well_formed(patches), "vol/patches must be non-empty float tensors with ld >= c");
   MSK_REQUIRE(ctx, vol.c == patches.c, "vol/patches channel mismatch");
   MSK_REQUIRE(ctx, origins != nullptr, "origins must be a host array of patches.n x 4 int32");
   MSK_REQUIRE(ctx, disjoint(vol, patches), "patches must not overlap vol");
   const SwDims g = dims_of(vol, patches);
   // the quad kernel stores whole patch quads and indexes the volume as dense (ld == c): a channel-slice view on either side takes
   // the element kernel
-  const bool quads = quad_dense(patches) && vol.ld == vol.c && ((long)g.rw * g.C) % 4 == 0;
+  const bool quads = msk_quad_dense(patches) && vol.ld == vol.c && ((long)g.rw * g.C) % 4 == 0;
   const long total = quads ? (long)g.rd * g.rh * (g.rw * (long)g.C / 4) : (long)g.rd * g.rh * g.rw * g.C;
   MSK_REQUIRE(ctx, blocks_for(total) <= INT_MAX, "window too large");
   SwBox b;
@@ -207,7 +203,7 @@ int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_
     float* dst = (float*)patches.p + k * wfloats;
     if (quads) {
       // whole source quads: dense volume whose rows and this window's row start are whole quads
-      const int src_quads = quad_dense(vol) && ((long)g.W * g.C) % 4 == 0 && ((long)b.w0 * g.C) % 4 == 0;
+      const int src_quads = msk_quad_dense(vol) && ((long)g.W * g.C) % 4 == 0 && ((long)b.w0 * g.C) % 4 == 0;
       SW_LAUNCH(sw_gather_quad_k, total, (const float*)vol.p, dst, g, b, cval, src_quads);
     } else {
       SW_LAUNCH(sw_gather_elem_k, total, (const float*)vol.p, vol.ld, dst, patches.ld, g, b, cval);
@@ -219,7 +215,7 @@ int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_
 
 int msk_sw_accumulate(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, const float* td, int nd, const float* th, int nh,
                       const float* tw, int nw, msk_tensor acc) {
-  MSK_REQUIRE(ctx, well_formed(logits) && well_formed(acc), "logits/acc must be non-empty float tensors with ld >= c");
+  MSK_REQUIRE(ctx, msk_well_formed(logits) && msk_well_formed(acc), "logits/acc must be non-empty float tensors with ld >= c");
   MSK_REQUIRE(ctx, logits.c == acc.c, "logits/acc channel mismatch");
   MSK_REQUIRE(ctx, origins != nullptr, "origins must be a host array of logits.n x 7 int32");
   MSK_REQUIRE(ctx, td != nullptr && th != nullptr && tw != nullptr && ((((uintptr_t)td) | ((uintptr_t)th) | ((uintptr_t)tw)) & 3) == 0,
@@ -236,7 +232,7 @@ int msk_sw_accumulate(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, c
     MSK_REQUIRE(ctx, clip_box(acc, logits, o, &b), "origins: a window does not intersect the volume");
   }
   msk_launch_scope ls(ctx, "sw_accumulate");
-  const bool dense = quad_dense(logits) && quad_dense(acc) && ((long)g.rw * g.C) % 4 == 0 && ((long)g.W * g.C) % 4 == 0;
+  const bool dense = msk_quad_dense(logits) && msk_quad_dense(acc) && ((long)g.rw * g.C) % 4 == 0 && ((long)g.W * g.C) % 4 == 0;
   const long wfloats = (long)g.rd * g.rh * g.rw * logits.ld;
   for (int k = 0; k < logits.n; ++k) {
     const int32_t* o = origins + 7 * k;

@@ -208,21 +208,9 @@ tta_finish_direct_k(const float* __restrict__ acc, int ald, long voxels, int C, 
   }
 }
 
-inline bool same_shape(const msk_tensor& a, const msk_tensor& b) {
-  return a.n == b.n && a.d == b.d && a.h == b.h && a.w == b.w && a.c == b.c;
-}
-inline bool well_formed(const msk_tensor& t) {
-  return t.p != nullptr && (((uintptr_t)t.p) & 3) == 0 && t.n >= 1 && t.d >= 1 && t.h >= 1 && t.w >= 1 && t.c >= 1 && t.ld >= t.c;
-}
-inline bool quad_dense(const msk_tensor& t) { return t.ld == t.c && (((uintptr_t)t.p) & 15) == 0; }
-inline int direct_blocks(long total, int num_cu) {
-  const long want = (total + kThreads - 1) / kThreads, cap = (long)num_cu * 16;
-  return (int)(want < cap ? (want > 0 ? want : 1) : cap);
-}
-
 // tile geometry of tta_tile_k; false: the tensors need the direct kernels
 bool tile_geom(const msk_tensor& src, const msk_tensor& dst, int mask, TtaGeom* g) {
-  if (!quad_dense(src) || !quad_dense(dst) || ((long)src.w * src.c) % 4 != 0) return false;
+  if (!msk_quad_dense(src) || !msk_quad_dense(dst) || ((long)src.w * src.c) % 4 != 0) return false;
   int tv = kTileFloats / src.c;
   if (tv > kThreads) tv = kThreads;
   if (tv < kMinTileVoxels) return false;
@@ -251,8 +239,8 @@ inline unsigned tile_count(const TtaGeom& g) { return (unsigned)(((g.rows + g.R 
 extern "C" {
 
 int msk_flip_axes(msk_ctx* ctx, msk_tensor src, msk_tensor dst, int mask) {
-  MSK_REQUIRE(ctx, well_formed(src) && well_formed(dst), "src/dst must be non-empty float tensors with ld >= c");
-  MSK_REQUIRE(ctx, same_shape(src, dst), "src/dst shape mismatch");
+  MSK_REQUIRE(ctx, msk_well_formed(src) && msk_well_formed(dst), "src/dst must be non-empty float tensors with ld >= c");
+  MSK_REQUIRE(ctx, msk_same_shape(src, dst), "src/dst shape mismatch");
   MSK_REQUIRE(ctx, mask >= 0 && mask <= 7, "mask must be in 0..7 (bit 0 = D, bit 1 = H, bit 2 = W)");
   MSK_REQUIRE(ctx, src.p != dst.p, "msk_flip_axes is out of place");
   TtaGeom g;
@@ -262,7 +250,7 @@ int msk_flip_axes(msk_ctx* ctx, msk_tensor src, msk_tensor dst, int mask) {
                        (float*)dst.p, g, 0);
   } else {
     const long total = msk_voxels(src) * src.c;
-    hipLaunchKernelGGL(flip_direct_k, dim3(direct_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(flip_direct_k, dim3(msk_ew_blocks(total, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                        (const float*)src.p, src.ld, (float*)dst.p, dst.ld, total, src.d, src.h, src.w, src.c, mask);
   }
   MSK_LAUNCH_CHECK(ctx);
@@ -270,8 +258,8 @@ int msk_flip_axes(msk_ctx* ctx, msk_tensor src, msk_tensor dst, int mask) {
 }
 
 int msk_tta_accumulate(msk_ctx* ctx, msk_tensor logits, int mask, msk_tensor acc, int first) {
-  MSK_REQUIRE(ctx, well_formed(logits) && well_formed(acc), "logits/acc must be non-empty float tensors with ld >= c");
-  MSK_REQUIRE(ctx, same_shape(logits, acc), "logits/acc shape mismatch");
+  MSK_REQUIRE(ctx, msk_well_formed(logits) && msk_well_formed(acc), "logits/acc must be non-empty float tensors with ld >= c");
+  MSK_REQUIRE(ctx, msk_same_shape(logits, acc), "logits/acc shape mismatch");
   MSK_REQUIRE(ctx, mask >= 0 && mask <= 7, "mask must be in 0..7 (bit 0 = D, bit 1 = H, bit 2 = W)");
   MSK_REQUIRE(ctx, logits.p != acc.p, "acc must not be the logits");
   TtaGeom g;
@@ -281,7 +269,7 @@ int msk_tta_accumulate(msk_ctx* ctx, msk_tensor logits, int mask, msk_tensor acc
                        (float*)acc.p, g, first ? 1 : 0);
   } else {
     const long voxels = msk_voxels(logits);
-    hipLaunchKernelGGL(tta_acc_direct_k, dim3(direct_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(tta_acc_direct_k, dim3(msk_ew_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                        (const float*)logits.p, logits.ld, (float*)acc.p, acc.ld, voxels, logits.d, logits.h, logits.w, logits.c,
                        mask, first ? 1 : 0);
   }
@@ -290,9 +278,9 @@ int msk_tta_accumulate(msk_ctx* ctx, msk_tensor logits, int mask, msk_tensor acc
 }
 
 int msk_tta_finish(msk_ctx* ctx, msk_tensor acc, int passes, msk_tensor probs, int32_t* pred) {
-  MSK_REQUIRE(ctx, well_formed(acc), "acc must be a non-empty float tensor with ld >= c");
+  MSK_REQUIRE(ctx, msk_well_formed(acc), "acc must be a non-empty float tensor with ld >= c");
   MSK_REQUIRE(ctx, passes >= 1, "passes must be >= 1");
-  MSK_REQUIRE(ctx, probs.p == nullptr || (well_formed(probs) && same_shape(acc, probs)), "acc/probs shape mismatch");
+  MSK_REQUIRE(ctx, probs.p == nullptr || (msk_well_formed(probs) && msk_same_shape(acc, probs)), "acc/probs shape mismatch");
   MSK_REQUIRE(ctx, (((uintptr_t)pred) & 3) == 0, "pred must be a 4-byte aligned device pointer");
   if (probs.p == nullptr && pred == nullptr) return 0;
   const float r = 1.f / (float)passes;
@@ -302,11 +290,11 @@ int msk_tta_finish(msk_ctx* ctx, msk_tensor acc, int passes, msk_tensor probs, i
   tv &= ~3;
   const long tiles = tv > 0 ? (voxels + tv - 1) / tv : 0;
   msk_launch_scope ls(ctx, "tta_finish");
-  if (quad_dense(acc) && (probs.p == nullptr || quad_dense(probs)) && tv >= kMinTileVoxels && tiles <= INT_MAX) {
+  if (msk_quad_dense(acc) && (probs.p == nullptr || msk_quad_dense(probs)) && tv >= kMinTileVoxels && tiles <= INT_MAX) {
     hipLaunchKernelGGL(tta_finish_tile_k, dim3((unsigned)tiles), dim3(kThreads), (size_t)tv * acc.c * sizeof(float), ctx->stream,
                        (const float*)acc.p, voxels, acc.c, tv, r, (float*)probs.p, pred);
   } else {
-    hipLaunchKernelGGL(tta_finish_direct_k, dim3(direct_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(tta_finish_direct_k, dim3(msk_ew_blocks(voxels, ctx->num_cu)), dim3(kThreads), 0, ctx->stream,
                        (const float*)acc.p, acc.ld, voxels, acc.c, r, (float*)probs.p, probs.p ? probs.ld : 0, pred);
   }
   MSK_LAUNCH_CHECK(ctx);

@@ -18,6 +18,8 @@ pytestmark = pytest.mark.gpu
 
 # a tail-only chunk, an exact chunk, one element over, and 257 chunks: the finish pass takes a second row
 N_LIST = [1, 3, 4, 4095, 4096, 4097, 10007, 1048581]
+# 2053 chunks: every lane of the finish pass takes one eight-deep round of loads, lanes 0..4 one more term
+N_FINISH = 2052 * 4096 + 7
 V = C.c_void_p
 F = C.c_float
 INF = float("inf")
@@ -62,7 +64,7 @@ def _ulp_apart(a, b, dtype):
 def test_record_equals_the_statement(scale):
     d = dev()
     bites = 0
-    for n in N_LIST:
+    for n in N_LIST + [N_FINISH]:
         g = vec(_grad(n, scale))
         ws, rec = _workspace(n), dmalloc(32)
         for gs in (1.0, 0.5):
@@ -82,7 +84,23 @@ def test_record_equals_the_statement(scale):
         assert np.array_equal(d.d2h(g, (n,), np.float32), _grad(n, scale))
         for p in (g, ws, rec):
             dfree(p)
-    assert bites == 2 * len(N_LIST)
+    assert bites == 2 * (len(N_LIST) + 1)
+
+
+def test_coef_and_intensity_stats_share_one_sum():
+    """msk_grad_clip_coef and msk_intensity_stats are two instantiations of one reduction: the same sum of squares, bit for bit"""
+    d = dev()
+    for n in N_LIST + [N_FINISH]:
+        g = vec(_grad(n, 1e-3))
+        b = C.c_size_t(0)
+        assert d.lib.msk_intensity_stats_workspace(C.c_long(n), C.byref(b)) == 0
+        ws, rec, ws_stats, stats = _workspace(n), dmalloc(32), dmalloc(b.value), dmalloc(32)
+        _coef(g, n, 1.0, INF, ws, rec)
+        d.call("msk_intensity_stats", V(g), C.c_long(n), V(ws_stats), V(stats))
+        S, want = float(d.d2h(rec, (4,), np.float64)[0]), float(d.d2h(stats, (4,), np.float64)[3])
+        assert S == want and S > 0, (n, S, want)
+        for p in (g, ws, rec, ws_stats, stats):
+            dfree(p)
 
 
 def test_coef_argument_errors_launch_nothing():

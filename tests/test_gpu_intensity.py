@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 BIG = 37 * 190 * 187                       # 321 chunks: more than the finish pass has lanes; crosses 2^20 voxels
 N_LIST = [1, 3, 255, 256, 257, 4095, 4096, 4097, 256 * 4096 + 1, BIG]
 N_SHORT = [1, 257, 4097, BIG]
+N_FINISH = 2052 * 4096 + 7                  # 2053 chunks: every lane of the finish pass takes one eight-deep round, lanes 0..4 one more term
 V = C.c_void_p
 
 
@@ -96,7 +97,7 @@ def _apply(x, y, n, mode, params, rec_a=None, rec_b=None, seed=0):
 @pytest.mark.parametrize("kind", ["normal", "negative", "positive", "constant", "offset"])
 def test_stats_equal_the_statement(kind, offset):
     d = dev()
-    for n in N_LIST:
+    for n in N_LIST + ([N_FINISH] if kind == "normal" else []):
         x, x_base = _up(_data(kind, n), offset)
         ws, rec1, rec2 = _workspace(n), dmalloc(32), dmalloc(32)
         d.call("msk_intensity_stats", V(x), C.c_long(n), V(ws), V(rec1))
