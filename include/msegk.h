@@ -596,6 +596,31 @@ int msk_bce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int igno
 int msk_bce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const double* stats,
                 float coef, int accumulate, msk_tensor dlogits);
 
+/* Region losses under a mask (SoftDiceLoss, TverskyLoss, FocalLoss, DiceCELoss; tests/region_reference.py is the statement):
+ * L = coef_r L_r + coef_f L_f, the coefficients given to the backward call.  Per voxel m = (label != ignore_index),
+ * t_c = (label == c) (C == 1: label == 1; a label outside [0, C) gives an all-zero row), p = softmax over the classes
+ * (activation 0, C >= 2) or sigmoid (activation 1).  Per group g (the batch when batch_dice != 0, else each sample; G groups)
+ * and class c: TP = sum m p t, SP = sum m p^q (q = 2 when squared_pred != 0, else 1), ST = sum m t.
+ *   mode 0 (Dice):    score = (2 TP + smooth) / max(SP + ST + smooth, 1e-8)
+ *   mode 1 (Tversky): score = (TP + smooth) / (TP + alpha (SP - TP) + beta (ST - TP) + smooth)     (q = 1 only)
+ *   L_r = 1 - mean of score over the groups and the scored classes K (all classes, or 1 .. C-1 when do_bg == 0 and C > 1)
+ *   dL_r/dp = m (A t + B q p^(q-1)),  A = -(dscore/dTP) / (G |K|),  B = -(dscore/dSP) / (G |K|),  both 0 outside K
+ *   L_f (focal_on != 0, softmax only) = sum v w_y (1 - u)^gamma (-log u) / sum v w_y over the voxels v with m = 1 and
+ *   0 <= label < C, u = p_label, w = weight (device, [C]) or ones when NULL; 0 when the denominator is 0.  gamma = 0 is plain
+ *   cross entropy; gamma must be 0 or >= 1.  The logits are used as given.
+ * out (device, 2 + C floats) = {L_f, L_r, mean over the groups of score[., c] for every class c}.
+ * stats (device, 5 G C + 2 doubles) = TP[G][C], SP[G][C], ST[G][C], A[G][C], B[G][C], f_num, f_den.
+ * Nothing is downloaded and nothing synchronises.  With several ranks the sums are those of the calling rank. */
+int msk_region_loss_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, int activation,
+                        int squared_pred, int batch_dice, int do_bg, int mode, float smooth, float alpha, float beta,
+                        int focal_on, float gamma, const float* weight, float* out, double* stats);
+/* dlogits (+)= coef_f dL_f/dlogits + coef_r dL_r/dlogits from the stats of the forward call with the same settings
+ * (accumulate != 0 adds: a region loss after CE / Dice on the same logits).  dlogits has the logits' shape. */
+int msk_region_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, int activation,
+                        int squared_pred, int batch_dice, int do_bg, int mode, float smooth, float alpha, float beta,
+                        int focal_on, float gamma, const float* weight, const double* stats, float coef_f, float coef_r,
+                        int accumulate, msk_tensor dlogits);
+
 /* ---- optimizer --------------------------------------------------------------- */
 /* paddle.optimizer.Momentum(momentum, weight_decay=L2) over one flat arena
  * (cvlibs/config.py:212-214): g += wd*p; v = mu*v + g; p -= lr*v.

@@ -151,6 +151,8 @@ SIGNATURES = {
     "msk_loss_bwd_ex": (_i, [_vp, _T, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _T]),
     "msk_bce_fwd": (_i, [_vp, _T, _vp, _i, _i, _i, _f, _vp, _vp]),
     "msk_bce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _i, _T]),
+    "msk_region_loss_fwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _vp]),
+    "msk_region_loss_bwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _i, _T]),
     "msk_sgd_momentum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_eager": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_finish": (_i, [_vp]),

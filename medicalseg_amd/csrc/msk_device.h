@@ -57,6 +57,20 @@ __device__ __forceinline__ void msk_tile_store(float* __restrict__ dst, int nqua
   }
 }
 
+// flat form of msk_tile_load for records that are not whole quads (3 classes: 12 bytes): the tile's floats are copied as they
+// lie (16-byte accesses, scalar tail), a thread's record starts at float tid * C -- an odd stride for C = 3: conflict-free
+// (the loss kernels of msk_loss_optim.hip and msk_loss_region.hip)
+__device__ __forceinline__ void tile_load_flat(const float* __restrict__ src, int nfloats, float* __restrict__ tile) {
+  const int nq = nfloats >> 2;
+  for (int i = threadIdx.x; i < nq; i += blockDim.x) reinterpret_cast<float4*>(tile)[i] = reinterpret_cast<const float4*>(src)[i];
+  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) tile[i] = src[i];
+}
+__device__ __forceinline__ void tile_store_flat(float* __restrict__ dst, int nfloats, const float* __restrict__ tile) {
+  const int nq = nfloats >> 2;
+  for (int i = threadIdx.x; i < nq; i += blockDim.x) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(tile)[i];
+  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) dst[i] = tile[i];
+}
+
 // splitmix64: the word of the counter RNGs (Dropout3D masks in msk_elementwise.hip, Gaussian noise in msk_intensity.hip)
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

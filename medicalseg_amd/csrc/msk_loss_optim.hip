@@ -199,18 +199,7 @@ loss_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labe
 // reductions per voxel and leave 12 of 32 lanes idle: 0.45 + 0.49 ms per output at 512 x 512 x 12, four outputs with deep
 // supervision).  A thread owns a voxel: its C logits sit in registers (float4 loads), softmax / sigmoid run over them in
 // place, the per-class sums are per-thread registers reduced once per block.
-// flat form of msk_tile_load for records that are not whole quads (3 classes: 12 bytes): the tile's floats are copied as they
-// lie (16-byte accesses, scalar tail), a thread's record starts at float tid * C -- an odd stride for C = 3: conflict-free
-__device__ __forceinline__ void tile_load_flat(const float* __restrict__ src, int nfloats, float* __restrict__ tile) {
-  const int nq = nfloats >> 2;
-  for (int i = threadIdx.x; i < nq; i += blockDim.x) reinterpret_cast<float4*>(tile)[i] = reinterpret_cast<const float4*>(src)[i];
-  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) tile[i] = src[i];
-}
-__device__ __forceinline__ void tile_store_flat(float* __restrict__ dst, int nfloats, const float* __restrict__ tile) {
-  const int nq = nfloats >> 2;
-  for (int i = threadIdx.x; i < nq; i += blockDim.x) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(tile)[i];
-  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) dst[i] = tile[i];
-}
+// (records that are not whole quads travel through tile_load_flat / tile_store_flat of msk_device.h)
 
 // ST (round 4): dense logits (ld == C, C % 4 == 0) travel through an LDS tile of 256 voxel records with whole-line accesses
 // (msk_tile_load) -- a lane reading its own 80-byte record straight from HBM held these passes at 1.0 / 1.9 TB/s.

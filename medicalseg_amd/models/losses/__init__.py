@@ -3,3 +3,4 @@ from .cross_entropy_loss import CrossEntropyLoss
 from .dice_loss import DiceLoss
 from .mixes_losses import MixedLoss
 from .binary_cross_entropy_loss import BCELoss
+from .region_losses import DiceCELoss, FocalLoss, SoftDiceLoss, TverskyLoss

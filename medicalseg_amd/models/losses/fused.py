@@ -128,12 +128,81 @@ def bce_node_for(logits: Tensor, labels, ignore_index, weight_mode, pos_weight_m
 
 _BCE_CACHE = {}
 
+REGION_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}
+REGION_DICE, REGION_TVERSKY = 0, 1
+
+
+class RegionNode:
+    """Masked soft Dice / Tversky (the 'dice' term, out[1]) and the focal / CE term (the 'ce' term, out[0]) for one
+    (logits, labels, settings) tuple: msk_region_loss_fwd / msk_region_loss_bwd, one statistics pass and one gradient pass
+    for both terms.  out[2:] is the per-class Dice; the record has 2 + C floats like LossNode's.  `settings` is the tuple
+    (ignore_index, activation, squared_pred, batch_dice, do_bg, mode, smooth, alpha, beta, focal_on, gamma) in the order of the
+    C ABI; `weight_ptr` is the device vector of per-class focal weights or None.  With several ranks the batch-Dice sums are
+    those of this rank's batch."""
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings, weight_ptr=None):
+        if tuple(labels.shape) != (logits.n, logits.d, logits.h, logits.w):
+            raise ValueError(f"label shape {labels.shape} does not match logits {logits.shape}")
+        self.logits, self.labels = logits, labels
+        self.dev = logits.dev
+        self.C = logits.c
+        self.settings = tuple(settings)
+        self.weight_ptr = weight_ptr
+        self.groups = 1 if self.settings[3] else logits.n
+        self.out_ptr = None
+        self.stats_ptr = None
+
+    def _args(self):
+        ign, act, sq, batch, bg, mode, smooth, alpha, beta, focal, gamma = self.settings
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(ign), int(act), int(sq), int(batch), int(bg), int(mode),
+                C.c_float(smooth), C.c_float(alpha), C.c_float(beta), int(focal), C.c_float(gamma), C.c_void_p(self.weight_ptr))
+
+    def evaluate(self):
+        if self.out_ptr is not None:
+            return
+        dev = self.dev
+        out = dev.arena.alloc((2 + self.C) * 4)
+        stats = dev.arena.alloc((5 * self.groups * self.C + 2) * 8)
+        dev.call("msk_region_loss_fwd", *self._args(), C.c_void_p(out), C.c_void_p(stats))
+        self.out_ptr, self.stats_ptr = out, stats
+
+    def backward(self, coef_f: float, coef_r: float, dz: Tensor | None = None) -> Tensor:
+        """coef_f dL_f/dlogits + coef_r dL_r/dlogits written into a new tensor, or added into `dz` (the CE / Dice gradient of
+        the same logits)."""
+        self.evaluate()
+        accumulate = dz is not None
+        if dz is None:
+            dz = self.logits.empty_like()
+        self.dev.call("msk_region_loss_bwd", *self._args(), C.c_void_p(self.stats_ptr), C.c_float(coef_f), C.c_float(coef_r),
+                      int(accumulate), dz.msk())
+        self.logits.grad = dz
+        self.logits.grad_written = True
+        return dz
+
+
+def region_node_for(logits: Tensor, labels, settings, weight_ptr=None) -> RegionNode:
+    """The node of (logits, labels, settings): two region losses on one logits tensor share it (one forward and one backward
+    pass) only if every setting agrees."""
+    labels = to_tensor(labels, logits.dev)
+    settings = tuple(settings)
+    key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), settings, weight_ptr)
+    node = _REGION_CACHE.get(key)
+    if node is None or node.logits is not logits:
+        if len(_REGION_CACHE) > 8:
+            _REGION_CACHE.clear()
+        node = RegionNode(logits, labels, settings, weight_ptr)
+        _REGION_CACHE[key] = node
+    return node
+
+
+_REGION_CACHE = {}
+
 # which float of a node's out record a term reads
 TERM_SLOT = {"ce": 0, "dice": 1, "bce": 0}
 
 
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (LossNode, 'ce'|'dice') or (BCENode, 'bce').  Values stay on
+    """A scalar loss = sum_i coef_i * term_i, term = (LossNode | RegionNode, 'ce'|'dice') or (BCENode, 'bce').  Values stay on
     the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 
@@ -176,8 +245,8 @@ class Scalar:
     __float__ = value
 
     def backward(self):
-        # coefficients per node, the nodes grouped per logits tensor: the CE / Dice node writes dL/dlogits, every BCE node
-        # on the same logits adds into it (or writes it when it is the first)
+        # coefficients per node, the nodes grouped per logits tensor: the CE / Dice node writes dL/dlogits, every BCE or
+        # region node on the same logits adds into it (or writes it when it is the first)
         per_logits = {}
         for c, node, which in self.terms:
             group = per_logits.setdefault(id(node.logits), {})
@@ -194,9 +263,11 @@ class Scalar:
             for node, cce, cdice in group.values():
                 if isinstance(node, LossNode):
                     dz = node.backward(cce, cdice)
-            for node, coef, _ in group.values():
+            for node, coef, cdice in group.values():
                 if isinstance(node, BCENode):
                     dz = node.backward(coef, dz)
+                elif isinstance(node, RegionNode):
+                    dz = node.backward(coef, cdice, dz)
             logits = next(iter(group.values()))[0].logits
             prod = logits.producer
             if prod is not None:

@@ -1,15 +1,18 @@
 from ... import nn
 from ...cvlibs import manager
 
+# the members that return (loss, per_channel_dice)
+_DICE_LOSSES = ("DiceLoss", "SoftDiceLoss", "TverskyLoss", "DiceCELoss")
+
 
 @manager.LOSSES.add_component
 class MixedLoss(nn.Layer):
     """sum_i coef_i * loss_i over ONE logits tensor (reference losses/mixes_losses.py:23-60).
 
     forward returns ``(loss_list, per_channel_dice)``: the weighted terms stay separate so that
-    the train loop can log them individually; a member whose class is NAMED ``DiceLoss`` also
-    returns its per-class dice, which is passed through (the reference dispatches on the class
-    name too, :57).  Here every term is a device-side ``Scalar`` of the fused loss node."""
+    the train loop can log them individually; a member whose class is NAMED ``DiceLoss`` (or
+    ``SoftDiceLoss``, ``TverskyLoss``, ``DiceCELoss``) also returns its per-class dice, which is
+    passed through (the reference dispatches on the class name too, :57).  Here every term is a device-side ``Scalar`` of the fused loss node."""
 
     def __init__(self, losses, coef):
         super().__init__()
@@ -25,7 +28,7 @@ class MixedLoss(nn.Layer):
         terms, dice_per_class = [], None
         for weight, member in zip(self.coef, self.losses):
             value = member(logits, labels)
-            if type(member).__name__ == "DiceLoss":
+            if type(member).__name__ in _DICE_LOSSES:
                 value, dice_per_class = value
             terms.append(value * weight)
         return terms, dice_per_class

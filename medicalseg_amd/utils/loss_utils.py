@@ -6,6 +6,7 @@ user-defined losses with those names take the same branches."""
 from ..device import Tensor
 
 _EDGE_LOSSES = ('BCELoss', 'FocalLoss')
+_DICE_LOSSES = ('DiceLoss', 'SoftDiceLoss', 'TverskyLoss', 'DiceCELoss')   # they return (loss, per_channel_dice)
 
 
 def check_logits_losses(logits_list, losses):
@@ -20,7 +21,7 @@ def _score(kind, loss_fn, logits_list, i, labels, edges):
     logits = logits_list[i]
     if kind == 'MixedLoss':
         return loss_fn(logits, labels)
-    if kind == 'DiceLoss':
+    if kind in _DICE_LOSSES:
         value, dice = loss_fn(logits, labels)
         return [value], dice
     if kind in _EDGE_LOSSES and getattr(loss_fn, 'edge_label', False):

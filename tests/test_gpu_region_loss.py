@@ -1,0 +1,372 @@
+"""The region losses on the device (msk_region_loss_fwd / msk_region_loss_bwd, medicalseg_amd/csrc/msk_loss_region.hip)
+against the float64 statement tests/region_reference.py, and SoftDiceLoss / DiceCELoss inside the training stack.
+
+Bounds (those of tests/test_gpu_bce.py and tests/test_gpu_ops.py::test_loss_fwd_bwd; a float32 numpy evaluation of the
+statement lies within 1.7e-7 (loss) and 3.9e-7 of max|g| (gradient) of the float64 one at these shapes): the losses and the
+per-class Dice within 1e-5 relative, the gradient max-abs <= 2e-5 max|g| and relative L2 <= 1e-5, the {TP, SP, ST} record
+within 1e-6 relative with ST exact.  The scalar settings enter the statement as the float32 values the kernels hold."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import region_reference as R
+from helpers import dev, dfree, dmalloc, redzone_check, t_from_ncdhw, vec, vec_back, vp  # noqa: F401 (redzone_check: autouse)
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ACT = {"softmax": 0, "sigmoid": 1}
+f32 = lambda v: float(np.float32(v))
+SMOOTH, TVERSKY = f32(1e-5), (f32(0.3), f32(0.7))
+
+# (squared_pred, batch_dice, do_bg, tversky): every value of every option with every other option's values
+REGION = [(0, 1, 0, None), (1, 0, 1, None), (0, 0, 0, TVERSKY), (0, 1, 1, TVERSKY), (1, 1, 0, None), (0, 0, 1, None)]
+# (gamma, weighted) cycled along REGION for the softmax: all six pairs
+FOCAL = [(0.0, False), (1.0, True), (2.0, False), (0.0, True), (1.0, False), (2.0, True)]
+
+
+def _data(rng, shape, Cn):
+    N, D, H, W = shape
+    z = (rng.standard_normal((N, Cn, D, H, W)) * 2).astype(np.float32)
+    y = rng.integers(0, max(Cn, 2), (N, D, H, W)).astype(np.int32)
+    y[rng.random(y.shape) < 0.1] = 255
+    if Cn > 1:
+        y.flat[1] = Cn + 2                      # outside [0, C), not ignored: an all-zero target row
+    k = min(1, Cn - 1)                          # one voxel where the softmax saturates: u = 1, 1 - u = 0
+    y[0, 0, 0, 2] = k if Cn > 1 else 1
+    z[0, :, 0, 0, 2] = -30.0
+    z[0, k, 0, 0, 2] = 30.0
+    return z, y
+
+
+def _device_labels(y):
+    p = dmalloc(y.nbytes)
+    dev().h2d(p, y)
+    return p
+
+
+def _settings(activation, squared, batch, do_bg, tversky, focal_on, gamma):
+    a, b = tversky if tversky else (0.0, 0.0)
+    return (255, ACT[activation], int(squared), int(batch), int(do_bg), int(tversky is not None), C.c_float(SMOOTH), C.c_float(a),
+            C.c_float(b), int(focal_on), C.c_float(gamma))
+
+
+def _fwd(zt, yp, settings, wp, groups):
+    d = dev()
+    Cn = zt.c
+    out, stats = vec(np.zeros(2 + Cn)), dmalloc((5 * groups * Cn + 2) * 8)
+    d.call("msk_region_loss_fwd", zt.msk(), vp(yp), *settings, vp(wp), vp(out), vp(stats))
+    return vec_back(out, 2 + Cn), stats
+
+
+def _rel_ok(got, ref, tol=1e-5):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return bool(np.all(np.where(ref == 0, got == 0, np.abs(got - ref) <= tol * np.abs(ref))))
+
+
+def _grad_ok(got, ref):
+    """max-abs <= 2e-5 max|g| and relative L2 <= 1e-5"""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    scale = np.abs(ref).max()
+    if scale == 0:
+        return not got.any()
+    return np.abs(got - ref).max() <= 2e-5 * scale and np.linalg.norm(got - ref) <= 1e-5 * np.linalg.norm(ref)
+
+
+def _combos(Cn):
+    for i, (sq, batch, bg, tv) in enumerate(REGION):
+        if Cn > 1:
+            gamma, weighted = FOCAL[i]
+            yield "softmax", sq, batch, bg, tv, 1, gamma, weighted
+        yield "sigmoid", sq, batch, bg, tv, 0, 0.0, False
+
+
+@pytest.mark.parametrize("layout", ["dense", "dense_acc", "slice", "slice_acc"])
+@pytest.mark.parametrize("shape", [(1, 5, 7, 9), (3, 5, 7, 9), (2, 9, 16, 17), (2, 16, 16, 16)])
+@pytest.mark.parametrize("Cn", [1, 2, 3, 4, 8, 20, 33])
+def test_region_kernels_match_statement(Cn, shape, layout):
+    d = dev()
+    N, D, H, W = shape
+    rng = np.random.default_rng(Cn * 1000 + D * 10 + N)
+    z, y = _data(rng, shape, Cn)
+    yp = _device_labels(y)
+    w = rng.uniform(0.5, 2, Cn).astype(np.float32)
+    wp = vec(w)
+    sliced, acc = layout.startswith("slice"), layout.endswith("acc")
+    c0, wide = (1, Cn + 3) if sliced else (0, Cn)
+    zw = np.zeros((N, wide, D, H, W), np.float32)
+    zw[:, c0:c0 + Cn] = z
+    zt = t_from_ncdhw(zw).channel_slice(c0, c0 + Cn) if sliced else t_from_ncdhw(z)
+    coef_f, coef_r = 0.75, 1.25
+    for activation, sq, batch, bg, tv, focal_on, gamma, weighted in _combos(Cn):
+        tag = (activation, sq, batch, bg, tv, gamma, weighted)
+        G = 1 if batch else N
+        settings = _settings(activation, sq, batch, bg, tv, focal_on, gamma)
+        ref = R.region_loss(z, y, activation, bool(sq), bool(batch), bool(bg), SMOOTH, tv, coef_r, coef_f * focal_on, gamma,
+                            w if weighted else None)
+        out, stats = _fwd(zt, yp, settings, wp if weighted else None, G)
+        st = d.d2h(stats, (5 * G * Cn + 2,), np.float64)
+        print(tag, "L_f %.3e L_r %.3e" % (abs(out[0] - ref["L_f"]) / max(abs(ref["L_f"]), 1e-30),
+                                          abs(out[1] - ref["L_r"]) / max(abs(ref["L_r"]), 1e-30)))
+        assert _rel_ok(out[0], ref["L_f"]), (tag, out[0], ref["L_f"])
+        assert _rel_ok(out[1], ref["L_r"]), (tag, out[1], ref["L_r"])
+        assert _rel_ok(out[2:], ref["dice"]), (tag, out[2:], ref["dice"])
+        TP, SP, ST, A, B = (st[k * G * Cn:(k + 1) * G * Cn].reshape(G, Cn) for k in range(5))
+        assert _rel_ok(TP, ref["TP"], 1e-6) and _rel_ok(SP, ref["SP"], 1e-6), tag
+        assert np.array_equal(ST, ref["ST"]), tag
+        assert _rel_ok(A, ref["A"]) and _rel_ok(B, ref["B"]), tag
+        if not bg and Cn > 1:                    # the background class takes no part in the region term
+            assert not A[:, 0].any() and not B[:, 0].any()
+        if focal_on:
+            assert _rel_ok(st[-2:], [ref["f_num"], ref["f_den"]], 1e-6), tag
+        # dlogits: a channel slice of a wider buffer too; with accumulate the old values stay underneath
+        base = (rng.standard_normal((N, wide, D, H, W)) * np.abs(ref["grad"]).max()).astype(np.float32)
+        dw = t_from_ncdhw(base)
+        dt = dw.channel_slice(c0, c0 + Cn) if sliced else dw
+        d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, vp(wp if weighted else None), vp(stats), C.c_float(coef_f),
+               C.c_float(coef_r), int(acc), dt.msk())
+        got = dw.numpy()
+        if acc:    # as tests/test_gpu_bce.py: the stored sum against old + gradient, and the gradient's own max-abs bound
+            under = base[:, c0:c0 + Cn].astype(np.float64)
+            assert _grad_ok(got[:, c0:c0 + Cn], under + ref["grad"]), tag
+            assert np.abs(got[:, c0:c0 + Cn] - under - ref["grad"]).max() <= 2e-5 * np.abs(ref["grad"]).max(), tag
+        else:
+            assert _grad_ok(got[:, c0:c0 + Cn], ref["grad"]), tag
+            ignored = np.moveaxis(got[:, c0:c0 + Cn], 1, -1)[y == 255]
+            assert not ignored.any(), tag        # m = 0: exactly 0, whatever the terms
+        if sliced:   # the other channels of the wide buffer are untouched
+            assert np.array_equal(got[:, :c0], base[:, :c0]) and np.array_equal(got[:, c0 + Cn:], base[:, c0 + Cn:])
+        dfree(dw.ptr)
+        dfree(stats)
+
+
+@pytest.mark.parametrize("Cn", [3, 20])
+def test_focal_alone_is_zero_under_the_mask_and_matches(Cn):
+    d = dev()
+    rng = np.random.default_rng(Cn)
+    z, y = _data(rng, (2, 9, 16, 17), Cn)
+    yp, zt = _device_labels(y), t_from_ncdhw(z)
+    for gamma in (0.0, 1.0, 2.0, 3.5):
+        settings = _settings("softmax", 0, 1, 0, None, 1, gamma)
+        ref = R.region_loss(z, y, lambda_r=0.0, lambda_f=1.0, gamma=f32(gamma))
+        out, stats = _fwd(zt, yp, settings, None, 1)
+        assert _rel_ok(out[0], ref["L_f"]), (gamma, out[0], ref["L_f"])
+        dz = t_from_ncdhw(np.full_like(z, 7.0))
+        d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(0.0), 0, dz.msk())
+        got = dz.numpy()
+        assert _grad_ok(got, ref["grad"]), gamma
+        assert not np.moveaxis(got, 1, -1)[y == 255].any()
+
+
+@pytest.mark.parametrize("Cn", [1, 3])
+def test_all_voxels_ignored(Cn):
+    d = dev()
+    z = np.random.default_rng(5).standard_normal((2, Cn, 5, 7, 9)).astype(np.float32)
+    y = np.full((2, 5, 7, 9), 255, np.int32)
+    yp, zt = _device_labels(y), t_from_ncdhw(z)
+    for batch in (0, 1):
+        for tv in (None, TVERSKY):
+            act, focal_on = ("softmax", 1) if Cn > 1 else ("sigmoid", 0)
+            settings = _settings(act, 0, batch, 0, tv, focal_on, 2.0)
+            out, stats = _fwd(zt, yp, settings, None, 1 if batch else 2)
+            assert out[0] == 0.0 and out[1] == 0.0 and np.all(out[2:] == 1.0)
+            dz = t_from_ncdhw(np.full_like(z, 7.0))
+            d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(1.0), 0, dz.msk())
+            assert not dz.numpy().any()
+
+
+@pytest.mark.parametrize("Cn,batch", [(3, 1), (3, 0), (20, 1), (33, 0)])
+def test_two_calls_give_the_same_bits(Cn, batch):
+    d = dev()
+    shape = (2, 9, 16, 17)
+    z, y = _data(np.random.default_rng(11), shape, Cn)
+    yp, zt = _device_labels(y), t_from_ncdhw(z)
+    settings = _settings("softmax", 0, batch, 0, None, 1, 2.0)
+    G = 1 if batch else 2
+    runs = []
+    for _ in range(2):
+        out, stats = _fwd(zt, yp, settings, None, G)
+        dz = t_from_ncdhw(np.zeros_like(z))
+        d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(1.0), 0, dz.msk())
+        runs.append((out.view(np.uint32), d.d2h(stats, (5 * G * Cn + 2,), np.uint64), dz.numpy().view(np.uint32)))
+    for a, b in zip(*runs):
+        assert np.array_equal(a, b)
+
+
+def test_logits_under_the_mask_change_nothing_but_do_change_the_vnet_dice():
+    """The defect that motivates the masked losses: a shell of label 255 around the patch (what label_pad=255 leaves)."""
+    d = dev()
+    rng = np.random.default_rng(21)
+    Cn, shape = 3, (1, 8, 8, 8)
+    z = (rng.standard_normal((1, Cn) + shape[1:]) * 2).astype(np.float32)
+    y = rng.integers(0, Cn, shape).astype(np.int32)
+    shell = np.ones(shape, bool)
+    shell[:, 1:-1, 1:-1, 1:-1] = False
+    y[shell] = 255
+    z2 = z.copy()
+    np.moveaxis(z2, 1, -1)[shell] = (rng.standard_normal((int(shell.sum()), Cn)) * 5).astype(np.float32)
+    yp = _device_labels(y)
+    settings = _settings("softmax", 0, 1, 0, None, 1, 0.0)
+    ones = vec(np.ones(Cn))
+    res, vnet = [], []
+    for zz in (z, z2):
+        zt = t_from_ncdhw(zz)
+        out, stats = _fwd(zt, yp, settings, None, 1)
+        dz = t_from_ncdhw(np.zeros_like(zz))
+        d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(1.0), 0, dz.msk())
+        res.append((out.view(np.uint32), np.moveaxis(dz.numpy(), 1, -1)[~shell].view(np.uint32)))
+        # the same experiment through DiceLoss (sigmoid_norm=False): msk_loss_fwd_ex / msk_loss_bwd_ex
+        vout, vstats = vec(np.zeros(2 + Cn)), dmalloc((3 * Cn + 2) * 8)
+        d.call("msk_loss_fwd_ex", zt.msk(), vp(yp), vp(ones), 255, 1, None, vp(vout), vp(vstats))
+        vnet.append(vec_back(vout, 2 + Cn)[1])
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+    assert vnet[0] != vnet[1]                    # the V-Net Dice sums p^2 over the padding too: this test can fail
+
+
+def test_argument_errors_launch_nothing():
+    d = dev()
+    from medicalseg_amd._lib import MskError
+    rng = np.random.default_rng(3)
+    z3, z1 = rng.standard_normal((1, 3, 4, 4, 4)).astype(np.float32), rng.standard_normal((1, 1, 4, 4, 4)).astype(np.float32)
+    y = rng.integers(0, 2, (1, 4, 4, 4)).astype(np.int32)
+    yp = _device_labels(y)
+    t3, t1 = t_from_ncdhw(z3), t_from_ncdhw(z1)
+    t65 = t_from_ncdhw(rng.standard_normal((1, 65, 4, 4, 4)).astype(np.float32))
+    good = dict(activation="softmax", squared=0, batch=1, do_bg=0, tversky=None, focal_on=1, gamma=0.0)
+    bad = [(t1, {}, "at least 2 classes"), (t65, {}, r"\[1,64\]"), (t3, dict(activation="sigmoid"), "needs the softmax"),
+           (t3, dict(tversky=TVERSKY, squared=1), "squared_pred"), (t3, dict(gamma=0.5), "gamma"), (t3, dict(gamma=-1.0), "gamma")]
+    for zt, change, text in bad:
+        settings = _settings(**{**good, **change})
+        out, stats = vec(np.full(2 + zt.c, 7.0)), dmalloc((5 * zt.c + 2) * 8)
+        dz = t_from_ncdhw(np.full((1, zt.c, 4, 4, 4), 7.0, np.float32))
+        with pytest.raises(MskError, match=text):
+            d.call("msk_region_loss_fwd", zt.msk(), vp(yp), *settings, None, vp(out), vp(stats))
+        with pytest.raises(MskError, match=text):
+            d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(1.0), 0, dz.msk())
+        assert np.all(vec_back(out, 2 + zt.c) == 7.0) and np.all(dz.numpy() == 7.0)
+    settings = list(_settings(**good))
+    settings[6] = C.c_float(-1.0)
+    out, stats = vec(np.full(5, 7.0)), dmalloc(17 * 8)
+    with pytest.raises(MskError, match="smooth"):
+        d.call("msk_region_loss_fwd", t3.msk(), vp(yp), *settings, None, vp(out), vp(stats))
+    settings = _settings(**good)
+    with pytest.raises(MskError, match="null"):
+        d.call("msk_region_loss_fwd", t3.msk(), None, *settings, None, vp(out), vp(stats))
+    with pytest.raises(MskError, match="null"):
+        d.call("msk_region_loss_fwd", t3.msk(), vp(yp), *settings, None, None, vp(stats))
+    d.call("msk_region_loss_fwd", t3.msk(), vp(yp), *settings, None, vp(out), vp(stats))
+    for shape in ((1, 2, 4, 4, 4), (1, 3, 4, 4, 5)):
+        dz = t_from_ncdhw(np.full(shape, 7.0, np.float32))
+        with pytest.raises(MskError, match="shape"):
+            d.call("msk_region_loss_bwd", t3.msk(), vp(yp), *settings, None, vp(stats), C.c_float(1.0), C.c_float(1.0), 0, dz.msk())
+        assert np.all(dz.numpy() == 7.0)
+    assert np.all(vec_back(out, 5) != 7.0)
+
+
+# ---- the training stack ----------------------------------------------------------------------------------------------------------
+class _Capture:
+    """Stands in as the producer of a logits tensor: records the gradient Scalar.backward hands over (and passes it on)."""
+    num_outputs = 1
+
+    def __init__(self, inner=None):
+        self.inner, self.grads = inner, []
+
+    def backward(self, g):
+        self.grads.append(g.numpy())
+        if self.inner is not None:
+            self.inner.backward(g)
+
+
+def _labels(rng, shape, Cn):
+    y = rng.integers(0, Cn, shape).astype(np.int32)
+    y[rng.random(shape) < 0.1] = 255
+    return y
+
+
+def test_mixed_ce_softdice_gradient_is_the_sum_of_both_statements():
+    from medicalseg_amd.device import to_tensor
+    from medicalseg_amd.models import CrossEntropyLoss, MixedLoss, SoftDiceLoss, VNet
+    rng = np.random.default_rng(32)
+    model = VNet(num_classes=3)
+    model.train()
+    x = rng.standard_normal((1, 1, 16, 16, 16)).astype(np.float32)
+    y = _labels(rng, (1, 16, 16, 16), 3)
+    yt = to_tensor(y)
+    logits = model(x)[0]
+    z = logits.numpy()
+    cap = _Capture()
+    logits.producer = cap
+    mixed = MixedLoss([CrossEntropyLoss(weight=[1.0, 1.0, 1.0]), SoftDiceLoss()], [1, 0.5])
+    terms, dice = mixed(logits, yt)
+    sum(terms).backward()
+    # CrossEntropyLoss with unit weights is the focal term at gamma = 0 (its 1e-8 on every logit leaves the softmax as it is)
+    ce = R.region_loss(z, y, lambda_r=0.0, lambda_f=1.0)
+    sd = R.region_loss(z, y, smooth=SMOOTH)
+    want = ce["grad"] + 0.5 * sd["grad"]
+    assert np.abs(cap.grads[0] - want).max() <= 2e-5 * np.abs(want).max()
+    assert _rel_ok(float(terms[0]), ce["L_f"]) and _rel_ok(float(terms[1]), 0.5 * sd["L_r"])
+    assert _rel_ok(np.asarray(dice), sd["dice"])
+
+
+@pytest.mark.parametrize("deepsup", [False, True])
+def test_dicece_trains_vnet_and_vnet_deepsup(deepsup):
+    from medicalseg_amd import optimizer as optim
+    from medicalseg_amd.device import to_tensor
+    from medicalseg_amd.models import DiceCELoss, VNet, VNetDeepSup
+    from medicalseg_amd.utils import loss_computation
+    rng = np.random.default_rng(4)
+    model = VNetDeepSup(elu=False, in_channels=1, num_classes=3) if deepsup else VNet(num_classes=3)
+    model.train()
+    opt = optim.Momentum(1e-2, parameters=model.parameters(), momentum=0.9, weight_decay=1e-4)
+    n_out = 4 if deepsup else 1
+    losses = {"types": [DiceCELoss() for _ in range(n_out)], "coef": [1.0 / n_out] * n_out}
+    x = rng.standard_normal((1, 1, 16, 16, 16)).astype(np.float32)
+    y = _labels(rng, (1, 16, 16, 16), 3)
+    values = []
+    for step in range(2):
+        outs = model(x)
+        assert len(outs) == n_out
+        loss_list, dice = loss_computation(outs, to_tensor(y), losses)
+        assert len(loss_list) == n_out and np.asarray(dice).shape == (3,)
+        if step == 0:
+            for o, term in zip(outs, loss_list):
+                ref = R.region_loss(o.numpy(), y, smooth=SMOOTH, lambda_f=1.0)
+                assert _rel_ok(float(term), ref["loss"] / n_out)
+        loss = sum(loss_list)
+        loss.backward()
+        grads_finite = all(np.isfinite(p.grad_numpy()).all() for p in model.parameters()
+                           if p.arena is not None and p.arena.grad_ptr is not None)   # (the buffers' arena has no gradients)
+        opt.step()
+        values.append(float(loss))
+        assert grads_finite
+    assert np.all(np.isfinite(values)) and values[1] < values[0], values
+    assert all(np.isfinite(p.numpy()).all() for p in model.parameters())
+
+
+def test_train_and_evaluate_from_dicece_yaml(tmp_path):
+    import warnings
+
+    from medicalseg_amd import optimizer as optim
+    from medicalseg_amd.core import evaluate, train
+    from medicalseg_amd.cvlibs import Config
+    from medicalseg_amd.models import DiceCELoss, VNet
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")   # data_root warning
+        cfg = Config(os.path.join(ROOT, "configs", "synthetic", "vnet_synthetic_ct_patch_dicece_96.yml"))
+    cfg.dic["train_dataset"]["shape"] = [20, 16, 24]
+    cfg.dic["val_dataset"]["shape"] = [16, 16, 16]
+    crop = cfg.dic["train_dataset"]["transforms"][0]
+    assert crop["label_pad"] == 255
+    crop["size"] = [16, 16, 16]
+    ds, val = cfg.train_dataset, cfg.val_dataset
+    losses = cfg.loss
+    assert isinstance(losses["types"][0], DiceCELoss) and losses["types"][0].ignore_index == 255
+    model, opt = cfg.model, cfg.optimizer
+    assert isinstance(model, VNet) and isinstance(opt, optim.Momentum)
+    train(model, ds, val_dataset=val, optimizer=opt, save_dir=str(tmp_path / "out"), iters=2, batch_size=2,
+          save_interval=2, log_iters=1, losses=losses, keep_checkpoint_max=1)
+    assert os.path.exists(tmp_path / "out" / "iter_2" / "model.pdparams")
+    res = evaluate(model, val, losses, print_detail=True)
+    assert np.isfinite(res["mdice"])
