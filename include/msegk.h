@@ -825,6 +825,17 @@ int msk_interp_trilinear_fwd(msk_ctx* ctx, msk_tensor src, msk_tensor dst);
 int msk_interp_scratch_bytes(msk_ctx* ctx, msk_tensor src, msk_tensor dst, size_t* bytes);
 int msk_interp_trilinear_bwd(msk_ctx* ctx, msk_tensor ddst, msk_tensor dsrc, int accumulate,
                              void* scratch, size_t scratch_bytes);
+/* nnU-Net deep supervision scores every head at the head's own extent: the label [n, d, h, w] (device, int32) down-sampled by
+ * nearest neighbour to `levels` (1 .. 8) extents in ONE launch.  extents (host): levels x {od, oh, ow}, each in 1 .. the
+ * label's extent of that axis; dst (host): levels device pointers, level l of n*od*oh*ow int32.
+ *   dst_l[n, z, y, x] = label[n, iz, iy, ix],  per axis i = ((2 o + 1) * in) / (2 * out)   (integer division)
+ * which is the voxel-centre, extent-ratio geometry (align_corners=False) of msk_interp_trilinear_fwd, so it also serves an axis
+ * without an integer stride (12 -> 9); out == in is a copy.  The values travel as 32-bit patterns: ignore_index and anything
+ * else are neither interpreted nor clamped.  Errors (nothing is launched): an empty label, n*d*h*w >= 2^31, an axis longer than 32768 (the
+ * index arithmetic is 32-bit), levels outside 1 .. 8, an extent outside 1 .. in, a null or misaligned pointer, a destination
+ * that overlaps the label.  Nothing is downloaded and nothing synchronises (tests/pyramid_reference.py states the formula). */
+int msk_label_pyramid(msk_ctx* ctx, const int32_t* label, int n, int d, int h, int w, int levels, const int32_t* extents,
+                      int32_t* const* dst);
 
 /* ---- data parallel (RCCL over xGMI; core/train.py:81-85 fleet DataParallel) ---- */
 #define MSK_UNIQUE_ID_BYTES 128

@@ -180,6 +180,7 @@ SIGNATURES = {
     "msk_interp_trilinear_fwd": (_i, [_vp, _T, _T]),
     "msk_interp_scratch_bytes": (_i, [_vp, _T, _T, C.POINTER(_sz)]),
     "msk_interp_trilinear_bwd": (_i, [_vp, _T, _T, _i, _vp, _sz]),
+    "msk_label_pyramid": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "msk_dp_unique_id": (_i, [C.c_char_p]),
     "msk_dp_rccl_version": (_i, [C.POINTER(_i)]),
     "msk_dp_init": (_i, [_vp, C.c_char_p, _i, _i]),

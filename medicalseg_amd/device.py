@@ -239,7 +239,7 @@ class Tensor:
     ``shape`` reports the reference's logical NCDHW order so code written against the
     reference (``_, c, d, h, w = images.shape``; core/train.py:266) keeps working."""
 
-    __slots__ = ("dev", "ptr", "n", "d", "h", "w", "c", "ld", "gen", "grad", "grad_written", "grad_from", "producer", "out_index", "_amax", "_amax_gen", "_pool_bytes")
+    __slots__ = ("dev", "ptr", "n", "d", "h", "w", "c", "ld", "gen", "grad", "grad_written", "grad_from", "producer", "out_index", "native_head", "_amax", "_amax_gen", "_pool_bytes")
 
     def __init__(self, dev, ptr, n, d, h, w, c, ld=None, gen=None):
         self.dev, self.ptr = dev, ptr
@@ -254,6 +254,9 @@ class Tensor:
         self.grad_from = None
         self.producer = None
         self.out_index = 0
+        # set by a model that returns a deep-supervision head at the head's own extent: (extents of all its heads, this head's
+        # index); the losses then score it against that level of the label pyramid (models/losses/fused.py label_for)
+        self.native_head = None
         # device "amax array" (msk_amax_new) that the passes WRITING this tensor fold max |value| into, or None.  A channel
         # slice shares its parent's array (the parent's maximum is the maximum over its slices' writers); it is only handed
         # to a consumer by code that knows every channel was written by such a pass (nn.ConvBNAct / AddAct / copy_scale).

@@ -11,6 +11,46 @@ import numpy as np
 from ...device import IntTensor, LazyArray, Tensor, to_tensor
 
 
+def label_pyramid(labels: IntTensor, extents) -> list:
+    """The label [N, D, H, W] down-sampled by nearest neighbour to every (od, oh, ow) of `extents` (1 .. 8 of them) in one launch
+    of msk_label_pyramid: per axis i = ((2 o + 1) * in) // (2 * out), the values passed through as they are
+    (tests/pyramid_reference.py).  The levels come from the activation arena: they live until the next model forward, like
+    the loss records."""
+    dev = labels.dev
+    extents = [tuple(int(v) for v in e) for e in extents]
+    n, d, h, w = labels.shape
+    levels = [IntTensor(dev, dev.arena.alloc(n * od * oh * ow * 4), (n, od, oh, ow), dev.arena.gen) for od, oh, ow in extents]
+    ext = (C.c_int32 * (3 * len(extents)))(*[v for e in extents for v in e])
+    dst = (C.c_void_p * len(levels))(*[t.ptr for t in levels])
+    dev.call("msk_label_pyramid", C.c_void_p(labels.ptr), n, d, h, w, len(levels), ext, dst)
+    return levels
+
+
+_PYRAMID = {"key": None, "levels": None}
+
+
+def label_for(logits: Tensor, labels) -> IntTensor:
+    """The label a loss scores `logits` against: `labels` itself when the extents agree; for a head that its model returned at
+    the head's own extent (Tensor.native_head) the level of the label pyramid with that extent.  The first request after a
+    forward builds the levels of all heads of that model in one launch; they are kept per (label pointer, label shape, extents,
+    arena generation), one entry.  One launch per step therefore needs the SAME device label at every loss, as core/train.py and
+    loss_computation hand it over (one to_tensor per batch): a host array given to each loss separately is uploaded, and its
+    pyramid built, once per loss, and two native models scored alternately inside one arena generation rebuild it at every
+    change -- correct either way, only more launches."""
+    labels = to_tensor(labels, logits.dev)
+    if tuple(labels.shape) == (logits.n, logits.d, logits.h, logits.w):
+        return labels
+    mark = logits.native_head
+    if mark is None or len(labels.shape) != 4 or labels.shape[0] != logits.n:
+        raise ValueError(f"label shape {labels.shape} does not match logits {logits.shape}")
+    extents, index = mark
+    key = (labels.ptr, tuple(labels.shape), extents, logits.dev.arena.gen)
+    if _PYRAMID["key"] != key:
+        _PYRAMID["levels"] = label_pyramid(labels, extents)
+        _PYRAMID["key"] = key
+    return _PYRAMID["levels"][index]
+
+
 class LossNode:
     """Fused CE + Dice evaluation for one (logits, labels) pair."""
 
@@ -60,7 +100,7 @@ class LossNode:
 
 
 def node_for(logits: Tensor, labels) -> LossNode:
-    labels = to_tensor(labels, logits.dev)
+    labels = label_for(logits, labels)
     key = (labels.ptr, tuple(labels.shape))
     node = _NODE_CACHE.get((id(logits), logits.ptr, logits.gen) + key)
     if node is None or node.logits is not logits:
@@ -114,7 +154,7 @@ class BCENode:
 
 
 def bce_node_for(logits: Tensor, labels, ignore_index, weight_mode, pos_weight_mode, pos_weight) -> BCENode:
-    labels = to_tensor(labels, logits.dev)
+    labels = label_for(logits, labels)
     key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), int(ignore_index), int(weight_mode),
            int(pos_weight_mode), float(pos_weight))
     node = _BCE_CACHE.get(key)
@@ -183,7 +223,7 @@ class RegionNode:
 def region_node_for(logits: Tensor, labels, settings, weight_ptr=None) -> RegionNode:
     """The node of (logits, labels, settings): two region losses on one logits tensor share it (one forward and one backward
     pass) only if every setting agrees."""
-    labels = to_tensor(labels, logits.dev)
+    labels = label_for(logits, labels)
     settings = tuple(settings)
     key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), settings, weight_ptr)
     node = _REGION_CACHE.get(key)

@@ -4,6 +4,11 @@ resized to the input size with F.interpolate(mode='trilinear'); forward returns
 [out, d1, d2, d3] (loss coef 0.25 each,
 configs/mri_spine_seg/vnetdeepsup_mri_spine_seg_512_512_12_15k.yml:12-20).
 
+``native_heads=True`` is nnU-Net's form of deep supervision instead: in training the three heads are returned as their
+convolutions leave them, [out, h1, h2, h3], each marked (Tensor.native_head) so that the losses score it against the label
+down-sampled to its extent (models/losses/fused.py label_for); nothing is resized.  In eval mode the heads are not computed
+and forward returns [out].  Parameters and state dict are the same under either setting.
+
 The building blocks are the ones of models/vnet.py (the reference duplicates them verbatim,
 vnet_deepsup.py:32-175).  ``out_tr_all`` (:251) is constructed but never called by the
 reference's forward: its parameters are part of the state dict, never receive a gradient and
@@ -49,8 +54,9 @@ class VNetDeepSup(VNet):
 
     def __init__(self, elu=False, in_channels=1, num_classes=4, pretrained=None,
                  kernel_size=((2, 2, 2), (2, 2, 2), (2, 2, 2), (2, 2, 2)),
-                 stride_size=((2, 2, 2), (2, 2, 2), (2, 2, 2), (2, 2, 2))):
+                 stride_size=((2, 2, 2), (2, 2, 2), (2, 2, 2), (2, 2, 2)), native_heads=False):
         nn.Layer.__init__(self)
+        self.native_heads = bool(native_heads)
         self.best_loss = 1000000
         self.num_classes = num_classes
         self.in_channels = in_channels
@@ -97,30 +103,44 @@ class VNetDeepSup(VNet):
         out64 = self.down_tr64(out32)
         out128 = self.down_tr128(out64)
         out256 = self.down_tr256(out128)
+        native = self.native_heads
+        heads_on = self.training or not native      # nnU-Net switches deep supervision off for inference
+
+        def head(conv, feat):
+            if not heads_on:
+                return None, None
+            h = conv.run_forward(feat)
+            return h, (h if native else interpolate_trilinear(h, size))
+
         u256 = self.up_tr256(out256, out128)
-        h1 = self.out_tr256.run_forward(u256)
-        d1 = interpolate_trilinear(h1, size)
+        h1, d1 = head(self.out_tr256, u256)
         u128 = self.up_tr128(u256, out64)
-        h2 = self.out_tr128.run_forward(u128)
-        d2 = interpolate_trilinear(h2, size)
+        h2, d2 = head(self.out_tr128, u128)
         u64 = self.up_tr64(u128, out32)
-        h3 = self.out_tr64.run_forward(u64)
-        d3 = interpolate_trilinear(h3, size)
+        h3, d3 = head(self.out_tr64, u64)
         self._feat = self.up_tr32(u64, out16)
         out = self.out_tr32(self._feat)
         self._acts = (out16, out32, out64, out128, out256)
         self._ups = (u256, u128, u64)
         self._heads = (h1, h2, h3)
-        outs = [out, d1, d2, d3]
+        outs = [out, d1, d2, d3] if heads_on else [out]
         for i, t in enumerate(outs):
             t.producer, t.out_index = self, i
+        if native and heads_on:
+            extents = tuple((h.d, h.h, h.w) for h in self._heads)
+            for i, h in enumerate(self._heads):
+                h.native_head = (extents, i)
         return outs
 
     def _head_backward(self, conv, feat: Tensor, head: Tensor, dresized):
+        """dresized: the loss gradient of this head's output -- at the input extent, or with native_heads at the head's own"""
         if dresized is None:
             return
-        interpolate_trilinear_backward(dresized, head)
-        conv.run_backward(feat, head.grad, need_dx=True)
+        if self.native_heads:
+            conv.run_backward(feat, dresized, need_dx=True)
+        else:
+            interpolate_trilinear_backward(dresized, head)
+            conv.run_backward(feat, head.grad, need_dx=True)
         self._grads_ready(conv)
 
     def backward(self, dlogits):

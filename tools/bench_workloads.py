@@ -24,6 +24,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--iso", action="store_true", help="isotropic 2x2x2 kernels/strides (lung) instead of the MRI ones")
+    ap.add_argument("--native-heads", action="store_true",
+                    help="VNetDeepSup: the heads at their own extents against the down-sampled label (native_heads=True) instead "
+                         "of resized to the input extent")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT", help="msk_set_option knob for experiments")
     ap.add_argument("--eager-opt", type=int, default=1, choices=(0, 1), help="optimizer update per block during backward (Momentum.enable_eager; models with block hooks)")
     ap.add_argument("--inloop-preprocess", action="store_true",
@@ -47,7 +50,10 @@ def main():
     if a.model == "UNet3D":   # builder-defined (no reference model): python tools/bench_workloads.py --model UNet3D --shape 192,192,64 --num-classes 3 --batch 2
         model = models.UNet3D(num_classes=a.num_classes, base_channels=32, depth=4, precision=a.precision)
     else:
-        model = getattr(models, a.model)(num_classes=a.num_classes, kernel_size=K, stride_size=S)
+        if a.native_heads and a.model != "VNetDeepSup":
+            raise SystemExit("--native-heads: VNetDeepSup only")
+        kw = {"native_heads": True} if a.native_heads else {}
+        model = getattr(models, a.model)(num_classes=a.num_classes, kernel_size=K, stride_size=S, **kw)
     model.train()
     n_out = getattr(model, "num_outputs", 1)
     losses = {"types": [models.MixedLoss([models.CrossEntropyLoss(), models.DiceLoss()], [1, 1]) for _ in range(n_out)],
@@ -85,7 +91,7 @@ def main():
     dev.sync()
     ms = (time.perf_counter() - t0) * 1e3 / a.steps
     vox = a.batch * shape[0] * shape[1] * shape[2]
-    print(f"{a.model} {shape} ncls={a.num_classes} batch={a.batch}: {ms:.2f} ms/step, {vox / ms / 1e3:.2f} M voxels/s"
+    print(f"{a.model}{'(native_heads=True)' if a.native_heads else ''} {shape} ncls={a.num_classes} batch={a.batch}: {ms:.2f} ms/step, {vox / ms / 1e3:.2f} M voxels/s"
           + (" (per-kernel profiling on: serialised)" if a.profile_out else ""))
     if inloop:
         print(inloop["line"])
