@@ -17,7 +17,6 @@ import numpy as np
 
 from ..datasets import DataLoader
 from ..device import to_tensor
-from ..models.losses.fused import TERM_SLOT
 from ..optimizer import lr as lr_mod
 from ..parallel import DataParallel, ParallelEnv, init_parallel_env
 from ..utils import TimeAverager, calculate_eta, logger, loss_computation, resume, save, train_profiler
@@ -192,7 +191,7 @@ def _snapshot(dev, loss, loss_list, per_channel_dice):
         ptr = _ring_slot(dev, n)
         dev.d2d(ptr, node.out_ptr, n * 4)
         slots.append((ptr, node.C))
-    terms = [[(c, index[id(node)], TERM_SLOT[w]) for c, node, w in l.terms] for l in loss_list]
+    terms = [[(c, index[id(node)], node.slot(w)) for c, node, w in l.terms] for l in loss_list]
     dsc_slot = None
     if per_channel_dice is not None and hasattr(per_channel_dice, "ptr"):
         for i, node in enumerate(nodes):

@@ -70,6 +70,116 @@ __device__ __forceinline__ void tile_store_flat(float* __restrict__ dst, int nfl
   for (int i = threadIdx.x; i < nq; i += blockDim.x) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(tile)[i];
   for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) dst[i] = tile[i];
 }
+// tile_store_flat adding into dst
+__device__ __forceinline__ void tile_add_flat(float* __restrict__ dst, int nfloats, const float* __restrict__ tile) {
+  const int nq = nfloats >> 2;
+  for (int i = threadIdx.x; i < nq; i += blockDim.x) {
+    float4 r = reinterpret_cast<const float4*>(tile)[i];
+    const float4 o = reinterpret_cast<float4*>(dst)[i];
+    r.x += o.x; r.y += o.y; r.z += o.z; r.w += o.w;
+    reinterpret_cast<float4*>(dst)[i] = r;
+  }
+  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) dst[i] += tile[i];
+}
+
+// ---- the thread-per-voxel scaffold of the loss kernels ----------------------------------------------------------------------------
+// loss_stats_tpv_k / loss_bwd_tpv_k (msk_loss_optim.hip) and region_stats_k / region_bwd_k (msk_loss_region.hip): a thread owns a
+// voxel, its C <= CM logits sit in registers (CM: the class count rounded up in steps of a quad), a workgroup of kTpvThreads takes
+// tiles of kTpvThreads consecutive voxels, and the gradient record goes back the way the logits came.  The lane-per-class
+// kernels this form replaced for C > 4 spent two 32-lane shuffle reductions per voxel and left 12 of 32 lanes idle: 0.45 +
+// 0.49 ms per output of the 20-class MRI model at 512 x 512 x 12, four outputs with deep supervision.  ST is the way a record
+// travels:
+//   ST = 1  (round 4) dense logits (ld == C, C % 4 == 0) go through an LDS tile of 256 voxel records with whole-line accesses
+//           (msk_tile_load) -- a lane reading its own 80-byte record straight from HBM held these passes at 1.0 / 1.9 TB/s;
+//   ST = 2  the flat form for dense C <= 4 (tile_load_flat): the 3-class head of the lung model ran the lane-per-class kernels
+//           (four lanes per voxel, one idle, 192 bytes per load instruction: 60 + 67 us per step at 2 x 128^3);
+//   ST = 0  a lane's own loads and stores for channel-slice views (ld > C), unaligned pointers and everything else.
+// Only the movement is shared: every kernel keeps its own arithmetic, whose order is part of its result.  And a kernel takes a
+// piece only where the call leaves its registers, LDS and instruction stream (read in the assembly, register names aside) what
+// its own text gave.  That is: the tile size and the ladder everywhere; the fill in loss_stats_tpv_k, loss_bwd_tpv_k and
+// region_stats_k; the take in both region kernels; the store of the tile forms in region_bwd_k.  Through the other calls the
+// compiler scheduled the kernel differently: the take split loss_stats_tpv_k's wait for its arguments in two and, with a shared
+// block reduction, cost 0.4 us per launch at 3 classes; take and store moved loss_bwd_tpv_k's tuned register counts, the fill
+// region_bwd_k<12, 0>'s; a shared ST = 0 store and a shared block reduction reordered the region kernels.
+constexpr int kTpvThreads = 256;
+
+constexpr int tpv_pitch(int CM) { return (CM / 4) | 1; }   // quads between two records of the ST = 1 tile
+constexpr int tpv_tile_quads(int CM, int ST) { return ST == 1 ? kTpvThreads * tpv_pitch(CM) : (ST == 2 ? kTpvThreads * CM / 4 : 1); }
+
+// the nv records from src = the tile's first logit into the LDS tile, between two barriers (the first: the previous round's
+// reads or store pass of the tile are over).  Reached by every thread of the workgroup; ST = 0: nothing.
+template <int CM, int ST>
+__device__ __forceinline__ void tpv_fill(float4* __restrict__ tile, const float* __restrict__ src, int nv, int C) {
+  if (ST) {
+    __syncthreads();
+    if (ST == 2) tile_load_flat(src, nv * C, reinterpret_cast<float*>(tile));
+    else msk_tile_load(src, nv * (C >> 2), C >> 2, tpv_pitch(CM), tile);
+    __syncthreads();
+  }
+}
+
+// this thread's record into zz[0..C), zz[C..CM) = 0: from the tile (ST = 2, 1) or from zp = its first logit in memory (ST = 0,
+// element by element).  Only for a thread that has a voxel.
+template <int CM, int ST>
+__device__ __forceinline__ void tpv_take(float (&zz)[CM], const float4* __restrict__ tile, const float* __restrict__ zp, int C) {
+  if (ST == 2) {
+#pragma unroll
+    for (int c = 0; c < CM; ++c) zz[c] = c < C ? reinterpret_cast<const float*>(tile)[threadIdx.x * C + c] : 0.f;
+  } else if (ST == 1) {
+#pragma unroll
+    for (int c = 0; c < CM; c += 4) {
+      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < C) q = tile[threadIdx.x * tpv_pitch(CM) + (c >> 2)];
+      zz[c] = q.x; zz[c + 1] = q.y; zz[c + 2] = q.z; zz[c + 3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < CM; ++c) zz[c] = c < C ? zp[c] : 0.f;
+  }
+}
+
+// the gradient records back through the tile (reached by every thread): barrier (every thread has taken its record), the threads
+// with `mine` write g into the tile, barrier, the tile's nv records go to dz_tile = the tile's first gradient, added to what is
+// there with `accumulate`.  A record that no thread wrote is never stored (nv ends before it).  ST = 0: nothing, the caller
+// stores its own voxel's record.
+template <int CM, int ST>
+__device__ __forceinline__ void tpv_put(const float (&g)[CM], float4* __restrict__ tile, float* __restrict__ dz_tile,
+                                        int C, int nv, bool mine, bool accumulate) {
+  if (ST == 2) {
+    __syncthreads();
+    if (mine) {
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c < C) reinterpret_cast<float*>(tile)[threadIdx.x * C + c] = g[c];
+    }
+    __syncthreads();
+    if (accumulate) tile_add_flat(dz_tile, nv * C, reinterpret_cast<const float*>(tile));
+    else tile_store_flat(dz_tile, nv * C, reinterpret_cast<const float*>(tile));
+  } else if (ST == 1) {
+    __syncthreads();
+    if (mine) {
+#pragma unroll
+      for (int c = 0; c < CM; c += 4)
+        if (c < C) tile[threadIdx.x * tpv_pitch(CM) + (c >> 2)] = make_float4(g[c], g[c + 1], g[c + 2], g[c + 3]);
+    }
+    __syncthreads();
+    msk_tile_store(dz_tile, nv * (C >> 2), C >> 2, tpv_pitch(CM), tile, accumulate);
+  }
+}
+
+// the CM ladder: LAUNCH(CM, ST) for 4 < C <= 32 with the register arrays sized to the class count in steps of a quad (round 4:
+// 20 classes ran the 32-slot instantiation), ST = 1 where QUAD holds and 0 otherwise.  What goes to the ladder, and the forms
+// outside it (C <= 4, C > 32), is each file's own decision.
+#define MSK_TPV_LADDER(C_, QUAD_, LAUNCH)                    \
+  do {                                                       \
+    if ((C_) <= 8) { MSK_TPV_STEP(8, QUAD_, LAUNCH) }        \
+    else if ((C_) <= 12) { MSK_TPV_STEP(12, QUAD_, LAUNCH) } \
+    else if ((C_) <= 16) { MSK_TPV_STEP(16, QUAD_, LAUNCH) } \
+    else if ((C_) <= 20) { MSK_TPV_STEP(20, QUAD_, LAUNCH) } \
+    else if ((C_) <= 24) { MSK_TPV_STEP(24, QUAD_, LAUNCH) } \
+    else { MSK_TPV_STEP(32, QUAD_, LAUNCH) }                 \
+  } while (0)
+#define MSK_TPV_STEP(CM_, QUAD_, LAUNCH) if (QUAD_) LAUNCH(CM_, 1); else LAUNCH(CM_, 0);
 
 // splitmix64: the word of the counter RNGs (Dropout3D masks in msk_elementwise.hip, Gaussian noise in msk_intensity.hip)
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {

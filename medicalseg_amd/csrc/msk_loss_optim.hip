@@ -11,6 +11,7 @@
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kTpvThreads, "the tpv_* helpers of msk_device.h assume this workgroup");
 
 inline int pow2ceil(int v) {
   int p = 1;
@@ -195,22 +196,15 @@ loss_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labe
 }
 
 
-// ---- thread-per-voxel forms for C > 4 (20-class MRI model: the lane-per-class kernels above spend two 32-lane shuffle
-// reductions per voxel and leave 12 of 32 lanes idle: 0.45 + 0.49 ms per output at 512 x 512 x 12, four outputs with deep
-// supervision).  A thread owns a voxel: its C logits sit in registers (float4 loads), softmax / sigmoid run over them in
-// place, the per-class sums are per-thread registers reduced once per block.
-// (records that are not whole quads travel through tile_load_flat / tile_store_flat of msk_device.h)
-
-// ST (round 4): dense logits (ld == C, C % 4 == 0) travel through an LDS tile of 256 voxel records with whole-line accesses
-// (msk_tile_load) -- a lane reading its own 80-byte record straight from HBM held these passes at 1.0 / 1.9 TB/s.
-// ST = 2: the flat form for C <= 4 (tile_load_flat): the 3-class head of the lung model ran the lane-per-class kernels above
-// (four lanes per voxel, one idle, 192 bytes per load instruction: 60 + 67 us per step at 2 x 128^3).
+// ---- thread-per-voxel forms for C > 4 and for dense C <= 4: the scaffold of msk_device.h (tpv_*: how the records travel for
+// each ST, and the rates that fixed each form; with float4 loads where every record is 16-byte aligned, v4, in this file).  A thread owns a voxel: softmax / sigmoid run over its C logits in place, the
+// per-class sums are per-thread registers reduced once per block.
 template <int CM, int ST>
 __global__ void __launch_bounds__(kThreads)
 loss_stats_tpv_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labels, const float* __restrict__ weights,
                  int ignore_index, long voxels, int C, int CB, float* __restrict__ partial /*[nb][5][CB]*/, int dice_softmax) {
-  constexpr int P = (CM / 4) | 1;
-  __shared__ float4 tile[ST == 1 ? kThreads * P : (ST == 2 ? kThreads * CM / 4 : 1)];
+  constexpr int P = tpv_pitch(CM);
+  __shared__ float4 tile[tpv_tile_quads(CM, ST)];
   float aI[CM], aS[CM], aT[CM], cen = 0.f, ced = 0.f;
 #pragma unroll
   for (int c = 0; c < CM; ++c) aI[c] = aS[c] = aT[c] = 0.f;
@@ -218,17 +212,13 @@ loss_stats_tpv_k(const float* __restrict__ z, int ld, const int32_t* __restrict_
   const long ntile = (voxels + kThreads - 1) / kThreads;
   for (long it = blockIdx.x; it < ntile; it += gridDim.x) {
     const long v = it * kThreads + threadIdx.x;
-    if (ST) {
-      const long v0 = it * kThreads;
-      const int nv = (int)(voxels - v0 < kThreads ? voxels - v0 : kThreads);
-      __syncthreads();   // the previous tile's records have been taken
-      if (ST == 2) tile_load_flat(z + v0 * C, nv * C, reinterpret_cast<float*>(tile));
-      else msk_tile_load(z + v0 * C, nv * (C >> 2), C >> 2, P, tile);
-      __syncthreads();
-    }
+    const long v0 = it * kThreads;
+    tpv_fill<CM, ST>(tile, z + v0 * C, (int)(voxels - v0 < kThreads ? voxels - v0 : kThreads), C);
     if (v >= voxels) continue;   // (after the barriers: every thread of the block reaches them)
     float zz[CM];
     const float* zp = z + v * ld;
+    // tpv_take's text (and below the block reduction as text, not a shared call): through calls the kernel waits twice for its
+    // arguments at every wavefront start and the tail of the reduction is scheduled differently: + 0.4 us per launch at 3 classes
     if (ST == 2) {
 #pragma unroll
       for (int c = 0; c < CM; ++c) zz[c] = c < C ? reinterpret_cast<const float*>(tile)[threadIdx.x * C + c] : 0.f;
@@ -348,24 +338,20 @@ loss_bwd_tpv_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ 
   const float inv_den = cden != 0 ? (float)(1.0 / cden) : 0.f;
   const float kd = -coef_dice / (float)C;
   const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (lddz % 4 == 0) && (((((uintptr_t)z) | ((uintptr_t)dz)) & 15) == 0);
-  constexpr int P = (CM / 4) | 1;
-  __shared__ float4 tile[ST == 1 ? kThreads * P : (ST == 2 ? kThreads * CM / 4 : 1)];
+  constexpr int P = tpv_pitch(CM);
+  __shared__ float4 tile[tpv_tile_quads(CM, ST)];
   const long ntile = (voxels + kThreads - 1) / kThreads;
   for (long it = blockIdx.x; it < ntile; it += gridDim.x) {
     const long v = it * kThreads + threadIdx.x;
     const long v0 = it * kThreads;
     const int nv = (int)(voxels - v0 < kThreads ? voxels - v0 : kThreads);
-    if (ST) {
-      __syncthreads();   // the previous tile's store pass is done
-      if (ST == 2) tile_load_flat(z + v0 * C, nv * C, reinterpret_cast<float*>(tile));
-      else msk_tile_load(z + v0 * C, nv * (C >> 2), C >> 2, P, tile);
-      __syncthreads();
-    }
+    tpv_fill<CM, ST>(tile, z + v0 * C, nv, C);
     const bool mine = v < voxels;
     float zz[CM], g[CM];
 #pragma unroll
     for (int c = 0; c < CM; ++c) g[c] = 0.f;
     const float* zp = z + (mine ? v : 0) * ld;
+    // tpv_take's and (below) tpv_put's text: through the calls ten instantiations of this kernel change their register counts
     if (ST == 2) {
 #pragma unroll
       for (int c = 0; c < CM; ++c) zz[c] = (c < C && mine) ? reinterpret_cast<const float*>(tile)[threadIdx.x * C + c] : 0.f;
@@ -611,25 +597,20 @@ int msk_loss_fwd_ex(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, cons
   if (!partial) return -1;
   {
     msk_launch_scope ls(ctx, "loss_fwd_stats");
-    if (C > 4 && C <= 32) {  // thread-per-voxel form
-      const bool st = (ctx->tile_staging & 2) && logits.ld == C && C % 4 == 0 && (((uintptr_t)logits.p) & 15) == 0;
 #define LOSS_STATS_TPV(CM_, ST_)                                                                                               \
   hipLaunchKernelGGL((loss_stats_tpv_k<CM_, ST_>), dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)logits.p, logits.ld, \
                      labels, weights, ignore_index, voxels, C, CB, partial, dice_softmax)
-      // register arrays sized to the class count in steps of a quad (round 4: 20 classes ran the 32-slot instantiation)
-#define LOSS_STATS_CM(CM_) { if (st) LOSS_STATS_TPV(CM_, 1); else LOSS_STATS_TPV(CM_, 0); }
-      if (C <= 8) LOSS_STATS_CM(8) else if (C <= 12) LOSS_STATS_CM(12) else if (C <= 16) LOSS_STATS_CM(16)
-      else if (C <= 20) LOSS_STATS_CM(20) else if (C <= 24) LOSS_STATS_CM(24) else LOSS_STATS_CM(32)
-#undef LOSS_STATS_CM
-#undef LOSS_STATS_TPV
+    if (C > 4 && C <= 32) {  // thread-per-voxel form
+      const bool st = (ctx->tile_staging & 2) && logits.ld == C && C % 4 == 0 && (((uintptr_t)logits.p) & 15) == 0;
+      MSK_TPV_LADDER(C, st, LOSS_STATS_TPV);
     } else if (flat4) {
       // dense 2..4-class logits (the lung model's head): thread per voxel, records through a flat LDS tile
-      hipLaunchKernelGGL((loss_stats_tpv_k<4, 2>), dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)logits.p, logits.ld,
-                         labels, weights, ignore_index, voxels, C, CB, partial, dice_softmax);
+      LOSS_STATS_TPV(4, 2);
     } else {
       hipLaunchKernelGGL(loss_stats_k<1>, dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)logits.p,
                          logits.ld, labels, weights, ignore_index, voxels, C, CB, partial, dice_softmax);
     }
+#undef LOSS_STATS_TPV
     MSK_LAUNCH_CHECK(ctx);
   }
   {
@@ -656,27 +637,22 @@ int msk_loss_bwd_ex(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, cons
   const int blocks = msk_ew_blocks(voxels * CB, ctx->num_cu);   // CB lanes per voxel
   const int tb = msk_ew_blocks(voxels, ctx->num_cu);            // the thread-per-voxel forms
   msk_launch_scope ls(ctx, "loss_bwd");
-  if (C > 4 && C <= 32) {  // thread-per-voxel form
-    const bool st = (ctx->tile_staging & 2) && logits.ld == C && dlogits.ld == C && C % 4 == 0 &&
-                    ((((uintptr_t)logits.p) | ((uintptr_t)dlogits.p)) & 15) == 0;
 #define LOSS_BWD_TPV(CM_, ST_)                                                                                                  \
   hipLaunchKernelGGL((loss_bwd_tpv_k<CM_, ST_>), dim3(tb), dim3(kThreads), 0, ctx->stream, (const float*)logits.p, logits.ld, \
                      labels, weights, ignore_index, stats, coef_ce, coef_dice, (float*)dlogits.p, dlogits.ld, voxels, C,        \
                      dice_softmax, dice_weight)
-#define LOSS_BWD_CM(CM_) { if (st) LOSS_BWD_TPV(CM_, 1); else LOSS_BWD_TPV(CM_, 0); }
-    if (C <= 8) LOSS_BWD_CM(8) else if (C <= 12) LOSS_BWD_CM(12) else if (C <= 16) LOSS_BWD_CM(16)
-    else if (C <= 20) LOSS_BWD_CM(20) else if (C <= 24) LOSS_BWD_CM(24) else LOSS_BWD_CM(32)
-#undef LOSS_BWD_CM
-#undef LOSS_BWD_TPV
+  if (C > 4 && C <= 32) {  // thread-per-voxel form
+    const bool st = (ctx->tile_staging & 2) && logits.ld == C && dlogits.ld == C && C % 4 == 0 &&
+                    ((((uintptr_t)logits.p) | ((uintptr_t)dlogits.p)) & 15) == 0;
+    MSK_TPV_LADDER(C, st, LOSS_BWD_TPV);
   } else if ((ctx->tile_staging & 4) && C >= 2 && C <= 4 && logits.ld == C && dlogits.ld == C &&
              ((((uintptr_t)logits.p) | ((uintptr_t)dlogits.p)) & 15) == 0) {
-    hipLaunchKernelGGL((loss_bwd_tpv_k<4, 2>), dim3(tb), dim3(kThreads), 0, ctx->stream, (const float*)logits.p, logits.ld,
-                       labels, weights, ignore_index, stats, coef_ce, coef_dice, (float*)dlogits.p, dlogits.ld, voxels, C,
-                       dice_softmax, dice_weight);
+    LOSS_BWD_TPV(4, 2);
   } else
   hipLaunchKernelGGL(loss_bwd_k, dim3(blocks), dim3(kThreads), 0, ctx->stream, (const float*)logits.p,
                      logits.ld, labels, weights, ignore_index, stats, coef_ce, coef_dice, (float*)dlogits.p,
                      dlogits.ld, voxels, C, CB, dice_softmax, dice_weight);
+#undef LOSS_BWD_TPV
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }

@@ -13,9 +13,10 @@
 // Thread mapping: a thread owns a voxel (its C logits in registers), a workgroup takes tiles of 256 consecutive voxels.  A group
 // is the whole batch (batch_dice) or one sample; the tiles of a workgroup never leave its group (grid = groups x workgroups per
 // group, a grid-stride loop inside the group), so a partial record belongs to one group and A, B are uniform over a workgroup.
-// The logits travel in the three forms of loss_stats_tpv_k (msk_loss_optim.hip, where the rates that fixed each form are
-// written down): ST = 2 a flat LDS tile for dense C <= 4, ST = 1 msk_tile_load quads for dense C % 4 == 0, ST = 0 a lane's own
-// element loads for channel-slice views (ld > C), unaligned pointers and everything else.  A masked voxel costs its label only.
+// The logits travel in the three forms of the thread-per-voxel scaffold (tpv_* in msk_device.h, where the rates that fixed each
+// form are written down): ST = 2 a flat LDS tile for dense C <= 4, ST = 1 msk_tile_load quads for dense C % 4 == 0, ST = 0 a
+// lane's own element loads for channel-slice views (ld > C), unaligned pointers and everything else.
+// A masked voxel costs its label only.
 #include <cmath>
 
 #include "msk_common.h"
@@ -23,6 +24,7 @@
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kTpvThreads, "the tpv_* helpers of msk_device.h assume this workgroup");
 
 struct RegionCfg {
   int ignore_index;
@@ -40,38 +42,6 @@ struct RegionFin {
 
 // the class whose target is 1 at a voxel with label y, or one that no class index equals: C == 1 -> t = (y == 1)
 __device__ __forceinline__ int region_target_class(int y, int C) { return C == 1 ? (y == 1 ? 0 : -1) : y; }
-
-// tile_store_flat (msk_device.h) adding into dst
-__device__ __forceinline__ void tile_add_flat(float* __restrict__ dst, int nfloats, const float* __restrict__ tile) {
-  const int nq = nfloats >> 2;
-  for (int i = threadIdx.x; i < nq; i += blockDim.x) {
-    float4 r = reinterpret_cast<const float4*>(tile)[i];
-    const float4 o = reinterpret_cast<float4*>(dst)[i];
-    r.x += o.x; r.y += o.y; r.z += o.z; r.w += o.w;
-    reinterpret_cast<float4*>(dst)[i] = r;
-  }
-  for (int i = 4 * nq + threadIdx.x; i < nfloats; i += blockDim.x) dst[i] += tile[i];
-}
-
-// a voxel's record from the tile (ST = 2, 1) or from memory (ST = 0) into zz[0..C); zz[C..CM) = 0
-template <int CM, int ST>
-__device__ __forceinline__ void region_take(float (&zz)[CM], const float4* __restrict__ tile, const float* __restrict__ zp, int C) {
-  constexpr int P = (CM / 4) | 1;
-  if (ST == 2) {
-#pragma unroll
-    for (int c = 0; c < CM; ++c) zz[c] = c < C ? reinterpret_cast<const float*>(tile)[threadIdx.x * C + c] : 0.f;
-  } else if (ST == 1) {
-#pragma unroll
-    for (int c = 0; c < CM; c += 4) {
-      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < C) q = tile[threadIdx.x * P + (c >> 2)];
-      zz[c] = q.x; zz[c + 1] = q.y; zz[c + 2] = q.z; zz[c + 3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < CM; ++c) zz[c] = c < C ? zp[c] : 0.f;
-  }
-}
 
 // zz: logits -> probabilities.  Softmax also returns what the focal term needs: the sum of exponentials, the label's logit less
 // the maximum, its probability u, and the sum of the OTHER classes' probabilities (1 - u without a cancellation)
@@ -109,8 +79,7 @@ template <int CM, int ST>
 __global__ void __launch_bounds__(kThreads)
 region_stats_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labels, const float* __restrict__ weight,
                RegionCfg cfg, long seg_vox, int wps, int C, float* __restrict__ partial /*[groups * wps][3 C + 2]*/) {
-  constexpr int P = (CM / 4) | 1;
-  __shared__ float4 tile[ST == 1 ? kThreads * P : (ST == 2 ? kThreads * CM / 4 : 1)];
+  __shared__ float4 tile[tpv_tile_quads(CM, ST)];
   __shared__ float s_w[CM];
   if (threadIdx.x < CM) s_w[threadIdx.x] = (weight != nullptr && threadIdx.x < C) ? weight[threadIdx.x] : 1.f;
   __syncthreads();
@@ -127,15 +96,10 @@ region_stats_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ 
     const bool mine = (int)threadIdx.x < nv;
     const long v = v0 + (mine ? threadIdx.x : 0);
     const int y = mine ? labels[v] : cfg.ignore_index;   // asked for ahead of the tile: the two latencies overlap
-    if (ST) {
-      __syncthreads();   // the previous tile's records have been taken
-      if (ST == 2) tile_load_flat(z + v0 * C, nv * C, reinterpret_cast<float*>(tile));
-      else msk_tile_load(z + v0 * C, nv * (C >> 2), C >> 2, P, tile);
-      __syncthreads();
-    }
+    tpv_fill<CM, ST>(tile, z + v0 * C, nv, C);
     if (y == cfg.ignore_index) continue;    // m = 0 (or no voxel): adds to nothing (behind the barriers every thread reaches)
     float zz[CM];
-    region_take<CM, ST>(zz, tile, z + v * ld, C);
+    tpv_take<CM, ST>(zz, tile, z + v * ld, C);
     float se, zym, u, so;
     region_probs<CM>(zz, C, y, cfg.sigmoid != 0, se, zym, u, so);
     const int yc = region_target_class(y, C);
@@ -266,8 +230,7 @@ __global__ void __launch_bounds__(kThreads)
 region_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labels, const float* __restrict__ weight,
              RegionCfg cfg, const double* __restrict__ stats, int nseg, float coef_f, float coef_r, int accumulate,
              float* __restrict__ dz, int lddz, long seg_vox, int wps, int C) {
-  constexpr int P = (CM / 4) | 1;
-  __shared__ float4 tile[ST == 1 ? kThreads * P : (ST == 2 ? kThreads * CM / 4 : 1)];
+  __shared__ float4 tile[tpv_tile_quads(CM, ST)];
   __shared__ float s_a[CM], s_b[CM], s_w[CM];
   const int seg = blockIdx.x / wps, first = blockIdx.x - seg * wps;
   const int GC = nseg * C;
@@ -291,10 +254,10 @@ region_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ la
     const bool mine = (int)threadIdx.x < nv;
     const long v = v0 + (mine ? threadIdx.x : 0);
     const int y = mine ? labels[v] : cfg.ignore_index;   // asked for ahead of the tile: the two latencies overlap
-    if (ST) {
+    if (ST) {            // tpv_fill's text: the call costs region_bwd_k<12, 0> a register
       __syncthreads();   // the previous tile's store pass is done
       if (ST == 2) tile_load_flat(z + v0 * C, nv * C, reinterpret_cast<float*>(tile));
-      else msk_tile_load(z + v0 * C, nv * (C >> 2), C >> 2, P, tile);
+      else msk_tile_load(z + v0 * C, nv * (C >> 2), C >> 2, tpv_pitch(CM), tile);
       __syncthreads();
     }
     if (!ST && !mine) continue;
@@ -303,7 +266,7 @@ region_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ la
 #pragma unroll
       for (int c = 0; c < CM; ++c) zz[c] = 0.f;
     } else {
-      region_take<CM, ST>(zz, tile, z + v * ld, C);
+      tpv_take<CM, ST>(zz, tile, z + v * ld, C);
       float se, zym, u, so;
       region_probs<CM>(zz, C, y, cfg.sigmoid != 0, se, zym, u, so);
       const int yc = region_target_class(y, C);
@@ -344,25 +307,8 @@ region_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ la
           }
       }
     }
-    if (ST == 2) {
-      __syncthreads();   // every thread has taken its record
-      if (mine) {
-#pragma unroll
-        for (int c = 0; c < CM; ++c)
-          if (c < C) reinterpret_cast<float*>(tile)[threadIdx.x * C + c] = zz[c];
-      }
-      __syncthreads();
-      if (accumulate) tile_add_flat(dz + v0 * C, nv * C, reinterpret_cast<const float*>(tile));
-      else tile_store_flat(dz + v0 * C, nv * C, reinterpret_cast<const float*>(tile));
-    } else if (ST == 1) {
-      __syncthreads();   // every thread has taken its record
-      if (mine) {
-#pragma unroll
-        for (int c = 0; c < CM; c += 4)
-          if (c < C) tile[threadIdx.x * P + (c >> 2)] = make_float4(zz[c], zz[c + 1], zz[c + 2], zz[c + 3]);
-      }
-      __syncthreads();
-      msk_tile_store(dz + v0 * C, nv * (C >> 2), C >> 2, P, tile, accumulate != 0);
+    if (ST) {
+      tpv_put<CM, ST>(zz, tile, dz + v0 * C, C, nv, mine, accumulate != 0);
     } else {
       float* dp = dz + v * lddz;
 #pragma unroll
@@ -422,16 +368,11 @@ int region_check(msk_ctx* ctx, const msk_tensor& logits, const int32_t* labels, 
 
 // CM: register arrays sized to the class count in steps of a quad, as the CE + Dice kernels do; 33..64 classes take the
 // lane's-own-loads form only (a quad tile of 64 classes would be 68 KiB of LDS)
-#define REGION_DISPATCH(LAUNCH)                                                                         \
-  do {                                                                                                  \
-    if (C <= 4) { if (plan.st == 2) LAUNCH(4, 2); else LAUNCH(4, 0); }                                  \
-    else if (C <= 8) { if (plan.st == 1) LAUNCH(8, 1); else LAUNCH(8, 0); }                             \
-    else if (C <= 12) { if (plan.st == 1) LAUNCH(12, 1); else LAUNCH(12, 0); }                          \
-    else if (C <= 16) { if (plan.st == 1) LAUNCH(16, 1); else LAUNCH(16, 0); }                          \
-    else if (C <= 20) { if (plan.st == 1) LAUNCH(20, 1); else LAUNCH(20, 0); }                          \
-    else if (C <= 24) { if (plan.st == 1) LAUNCH(24, 1); else LAUNCH(24, 0); }                          \
-    else if (C <= 32) { if (plan.st == 1) LAUNCH(32, 1); else LAUNCH(32, 0); }                          \
-    else LAUNCH(64, 0);                                                                                 \
+#define REGION_DISPATCH(LAUNCH)                                        \
+  do {                                                                 \
+    if (C <= 4) { if (plan.st == 2) LAUNCH(4, 2); else LAUNCH(4, 0); } \
+    else if (C <= 32) MSK_TPV_LADDER(C, plan.st == 1, LAUNCH);         \
+    else LAUNCH(64, 0);                                                \
   } while (0)
 
 extern "C" {

@@ -1,6 +1,6 @@
 from ... import nn
 from ...cvlibs import manager
-from .fused import Scalar, bce_node_for
+from .fused import BCENode, Scalar, node_for
 
 _WEIGHT_MODES = {None: 0, 'dynamic': 1}
 _POS_WEIGHT_NONE, _POS_WEIGHT_VALUE, _POS_WEIGHT_DYNAMIC = 0, 1, 2
@@ -58,5 +58,5 @@ class BCELoss(nn.Layer):
                     'The type of `pos_weight` is wrong, it should be float or str, but it is {}'.format(type(self.pos_weight)))
 
     def forward(self, logit, label):
-        node = bce_node_for(logit, label, self.ignore_index, _WEIGHT_MODES[self.weight], self._pw_mode, self._pw_value)
+        node = node_for(BCENode, logit, label, (int(self.ignore_index), _WEIGHT_MODES[self.weight], self._pw_mode, self._pw_value))
         return Scalar([(1.0, node, "bce")])

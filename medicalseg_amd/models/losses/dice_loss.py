@@ -2,7 +2,8 @@ import numpy as np
 
 from ... import nn
 from ...cvlibs import manager
-from .fused import Scalar, node_for, per_channel_dice
+from .fused import LossNode, Scalar, node_for, per_channel_dice
+from .loss_utils import device_weights
 
 
 @manager.LOSSES.add_component
@@ -21,15 +22,13 @@ class DiceLoss(nn.Layer):
         self.eps = 1e-5
 
     def forward(self, logits, labels):
-        node = node_for(logits, labels)
-        node.dice_softmax = not self.sigmoid_norm
+        node = node_for(LossNode, logits, labels)
+        weight_ptr = None
         if self.weight is not None:
             if self.weight.size != logits.c:
                 raise ValueError("DiceLoss weight has %d entries for %d classes" % (self.weight.size, logits.c))
-            if self._weight_dev is None or self._weight_dev[0] is not logits.dev:
-                ptr = logits.dev.malloc(max(self.weight.size, 4) * 4)
-                logits.dev.h2d(ptr, self.weight)
-                self._weight_dev = (logits.dev, ptr)
-            node.dice_weight_ptr = self._weight_dev[1]
+            self._weight_dev = device_weights(logits.dev, self.weight, self._weight_dev)
+            weight_ptr = self._weight_dev[1]
+        node.set_dice(not self.sigmoid_norm, weight_ptr)
         loss = Scalar([(1.0, node, "dice")])
         return loss, per_channel_dice(node)

@@ -51,8 +51,12 @@ def label_for(logits: Tensor, labels) -> IntTensor:
     return _PYRAMID["levels"][index]
 
 
-class LossNode:
-    """Fused CE + Dice evaluation for one (logits, labels) pair."""
+class Node:
+    """One evaluation of (logits, labels, settings) by a pair of fused kernels.  The record `out_ptr` has 2 + C floats for
+    every kind: the two terms, then the per-class Dice (the train loop's snapshot copies all kinds alike).  A kind supplies
+    stats_doubles(), _forward(), _backward(coef_a, coef_b, accumulate, dz), SLOTS and `writes`."""
+    writes = False     # True: backward WRITES dL/dlogits and cannot add into one; such a node runs first on its logits
+    SLOTS = {}         # term name -> the float of the record it reads; slot 0 takes coef_a, slot 1 coef_b in backward
 
     def __init__(self, logits: Tensor, labels: IntTensor):
         if tuple(labels.shape) != (logits.n, logits.d, logits.h, logits.w):
@@ -60,190 +64,168 @@ class LossNode:
         self.logits, self.labels = logits, labels
         self.dev = logits.dev
         self.C = logits.c
-        self.weights_ptr = None
-        self.ignore_index = 255
-        self.dice_softmax = False      # DiceLoss(sigmoid_norm=False)
-        self.dice_weight_ptr = None    # DiceLoss(weight=[...]) on the device
         self.out_ptr = None
         self.stats_ptr = None
         self.evaluated_with = None
 
+    def slot(self, which: str) -> int:
+        return self.SLOTS[which]
+
+    def _key(self):
+        """the settings a later caller may still change; evaluate() runs the forward again when they differ"""
+        return ()
+
     def evaluate(self):
-        key = (self.weights_ptr, self.dice_softmax, self.dice_weight_ptr)
-        if self.evaluated_with == (key, self.ignore_index) and self.out_ptr is not None:
+        key = self._key()
+        if self.evaluated_with == key:
             return
-        dev, Cn = self.dev, self.C
         if self.out_ptr is None:
-            self.out_ptr = dev.arena.alloc((2 + Cn) * 4)
-            self.stats_ptr = dev.arena.alloc((3 * Cn + 2) * 8)
-        w = self.weights_ptr
-        if w is None:  # Dice alone: CE term unused, any weights do
-            w = dev.arena.alloc(Cn * 4)
-            dev.h2d(w, np.ones(Cn, dtype=np.float32))
-            self._dummy_w = w
-        dev.call("msk_loss_fwd_ex", self.logits.msk(), C.c_void_p(self.labels.ptr), C.c_void_p(w),
-                 int(self.ignore_index), int(self.dice_softmax), C.c_void_p(self.dice_weight_ptr),
-                 C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
-        self.evaluated_with = (key, self.ignore_index)
+            self.out_ptr = self.dev.arena.alloc((2 + self.C) * 4)
+            self.stats_ptr = self.dev.arena.alloc(self.stats_doubles() * 8)
+        self._forward()
+        self.evaluated_with = key
 
-    def backward(self, coef_ce: float, coef_dice: float):
-        self.evaluate()
-        dev = self.dev
-        w = self.weights_ptr if self.weights_ptr is not None else self._dummy_w
-        dz = self.logits.empty_like()
-        dev.call("msk_loss_bwd_ex", self.logits.msk(), C.c_void_p(self.labels.ptr), C.c_void_p(w),
-                 int(self.ignore_index), int(self.dice_softmax), C.c_void_p(self.dice_weight_ptr),
-                 C.c_void_p(self.stats_ptr), C.c_float(coef_ce), C.c_float(coef_dice), dz.msk())
-        self.logits.grad = dz
-        self.logits.grad_written = True
-        return dz
-
-
-def node_for(logits: Tensor, labels) -> LossNode:
-    labels = label_for(logits, labels)
-    key = (labels.ptr, tuple(labels.shape))
-    node = _NODE_CACHE.get((id(logits), logits.ptr, logits.gen) + key)
-    if node is None or node.logits is not logits:
-        if len(_NODE_CACHE) > 8:
-            _NODE_CACHE.clear()
-        node = LossNode(logits, labels)
-        _NODE_CACHE[(id(logits), logits.ptr, logits.gen) + key] = node
-    return node
-
-
-_NODE_CACHE = {}
-
-
-class BCENode:
-    """BCELoss evaluation for one (logits, labels, settings) tuple: msk_bce_fwd / msk_bce_bwd.  out[0] is the loss (the
-    record has 2 + C floats like LossNode's, so the train loop's snapshot copies both kinds alike)."""
-
-    def __init__(self, logits: Tensor, labels: IntTensor, ignore_index: int, weight_mode: int, pos_weight_mode: int,
-                 pos_weight: float):
-        if tuple(labels.shape) != (logits.n, logits.d, logits.h, logits.w):
-            raise ValueError(f"label shape {labels.shape} does not match logits {logits.shape}")
-        self.logits, self.labels = logits, labels
-        self.dev = logits.dev
-        self.C = logits.c
-        self.ignore_index = int(ignore_index)
-        self.weight_mode, self.pos_weight_mode, self.pos_weight = int(weight_mode), int(pos_weight_mode), float(pos_weight)
-        self.out_ptr = None
-        self.stats_ptr = None
-
-    def evaluate(self):
-        if self.out_ptr is not None:
-            return
-        dev = self.dev
-        out = dev.arena.alloc((2 + self.C) * 4)
-        stats = dev.arena.alloc(8 * 8)
-        dev.call("msk_bce_fwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index, self.weight_mode,
-                 self.pos_weight_mode, C.c_float(self.pos_weight), C.c_void_p(out), C.c_void_p(stats))
-        self.out_ptr, self.stats_ptr = out, stats
-
-    def backward(self, coef: float, dz: Tensor | None = None) -> Tensor:
-        """coef * dBCE/dlogits written into a new tensor, or added into `dz` (the CE / Dice gradient of the same logits)."""
+    def backward(self, coef_a: float, coef_b: float, dz: Tensor | None = None) -> Tensor:
+        """coef_a d(term of slot 0)/dlogits + coef_b d(term of slot 1)/dlogits written into a new tensor (dz None), or added
+        into `dz`, the gradient the earlier nodes of the same logits left."""
+        assert dz is None or not self.writes
         self.evaluate()
         accumulate = dz is not None
         if dz is None:
             dz = self.logits.empty_like()
-        self.dev.call("msk_bce_bwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index,
-                      C.c_void_p(self.stats_ptr), C.c_float(coef), int(accumulate), dz.msk())
+        self._backward(coef_a, coef_b, int(accumulate), dz)
+        return self._publish(dz)
+
+    def _publish(self, dz: Tensor) -> Tensor:
         self.logits.grad = dz
         self.logits.grad_written = True
         return dz
 
 
-def bce_node_for(logits: Tensor, labels, ignore_index, weight_mode, pos_weight_mode, pos_weight) -> BCENode:
-    labels = label_for(logits, labels)
-    key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), int(ignore_index), int(weight_mode),
-           int(pos_weight_mode), float(pos_weight))
-    node = _BCE_CACHE.get(key)
-    if node is None or node.logits is not logits:
-        if len(_BCE_CACHE) > 8:
-            _BCE_CACHE.clear()
-        node = BCENode(logits, labels, ignore_index, weight_mode, pos_weight_mode, pos_weight)
-        _BCE_CACHE[key] = node
-    return node
+class LossNode(Node):
+    """Fused CE + Dice evaluation for one (logits, labels) pair: msk_loss_fwd_ex / msk_loss_bwd_ex.  CrossEntropyLoss and
+    DiceLoss share the node and each hands over its own settings."""
+    writes = True
+    SLOTS = {"ce": 0, "dice": 1}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings=()):
+        assert not settings, "LossNode takes its settings through set_ce / set_dice: two losses share one node"
+        super().__init__(logits, labels)
+        self.weights_ptr = None
+        self.ignore_index = 255
+        self.dice_softmax = False      # DiceLoss(sigmoid_norm=False)
+        self.dice_weight_ptr = None    # DiceLoss(weight=[...]) on the device
+
+    def set_ce(self, weights_ptr, ignore_index):
+        self.weights_ptr, self.ignore_index = weights_ptr, ignore_index
+
+    def set_dice(self, softmax: bool, weight_ptr=None):
+        """weight_ptr None leaves the vector an earlier DiceLoss on this node gave"""
+        self.dice_softmax = softmax
+        if weight_ptr is not None:
+            self.dice_weight_ptr = weight_ptr
+
+    def stats_doubles(self):
+        return 3 * self.C + 2
+
+    def _key(self):
+        return ((self.weights_ptr, self.dice_softmax, self.dice_weight_ptr), self.ignore_index)
+
+    def _args(self, w):
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), C.c_void_p(w), int(self.ignore_index), int(self.dice_softmax),
+                C.c_void_p(self.dice_weight_ptr))
+
+    def _forward(self):
+        w = self.weights_ptr
+        if w is None:  # Dice alone: CE term unused, any weights do
+            w = self.dev.arena.alloc(self.C * 4)
+            self.dev.h2d(w, np.ones(self.C, dtype=np.float32))
+            self._dummy_w = w
+        self.dev.call("msk_loss_fwd_ex", *self._args(w), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef_ce, coef_dice, accumulate, dz):
+        w = self.weights_ptr if self.weights_ptr is not None else self._dummy_w
+        self.dev.call("msk_loss_bwd_ex", *self._args(w), C.c_void_p(self.stats_ptr), C.c_float(coef_ce), C.c_float(coef_dice),
+                      dz.msk())
 
 
-_BCE_CACHE = {}
+class BCENode(Node):
+    """BCELoss evaluation: msk_bce_fwd / msk_bce_bwd.  out[0] is the loss.  `settings` is (ignore_index, weight_mode,
+    pos_weight_mode, pos_weight)."""
+    SLOTS = {"bce": 0}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.ignore_index, self.weight_mode, self.pos_weight_mode, self.pos_weight = settings
+
+    def stats_doubles(self):
+        return 8
+
+    def _forward(self):
+        self.dev.call("msk_bce_fwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index, self.weight_mode,
+                      self.pos_weight_mode, C.c_float(self.pos_weight), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef, _, accumulate, dz):
+        self.dev.call("msk_bce_bwd", self.logits.msk(), C.c_void_p(self.labels.ptr), self.ignore_index,
+                      C.c_void_p(self.stats_ptr), C.c_float(coef), accumulate, dz.msk())
+
 
 REGION_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}
 REGION_DICE, REGION_TVERSKY = 0, 1
 
 
-class RegionNode:
-    """Masked soft Dice / Tversky (the 'dice' term, out[1]) and the focal / CE term (the 'ce' term, out[0]) for one
-    (logits, labels, settings) tuple: msk_region_loss_fwd / msk_region_loss_bwd, one statistics pass and one gradient pass
-    for both terms.  out[2:] is the per-class Dice; the record has 2 + C floats like LossNode's.  `settings` is the tuple
-    (ignore_index, activation, squared_pred, batch_dice, do_bg, mode, smooth, alpha, beta, focal_on, gamma) in the order of the
-    C ABI; `weight_ptr` is the device vector of per-class focal weights or None.  With several ranks the batch-Dice sums are
+class RegionNode(Node):
+    """Masked soft Dice / Tversky (the 'dice' term, out[1]) and the focal / CE term (the 'ce' term, out[0]):
+    msk_region_loss_fwd / msk_region_loss_bwd, one statistics pass and one gradient pass for both terms.  out[2:] is the
+    per-class Dice.  `settings` is the tuple (ignore_index, activation, squared_pred, batch_dice, do_bg, mode, smooth, alpha,
+    beta, focal_on, gamma) in the order of the C ABI, then the device vector of per-class focal weights or None: two region
+    losses on one logits tensor share a node only if every one of them agrees.  With several ranks the batch-Dice sums are
     those of this rank's batch."""
+    SLOTS = {"ce": 0, "dice": 1}
 
-    def __init__(self, logits: Tensor, labels: IntTensor, settings, weight_ptr=None):
-        if tuple(labels.shape) != (logits.n, logits.d, logits.h, logits.w):
-            raise ValueError(f"label shape {labels.shape} does not match logits {logits.shape}")
-        self.logits, self.labels = logits, labels
-        self.dev = logits.dev
-        self.C = logits.c
-        self.settings = tuple(settings)
-        self.weight_ptr = weight_ptr
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.settings, self.weight_ptr = tuple(settings[:-1]), settings[-1]
         self.groups = 1 if self.settings[3] else logits.n
-        self.out_ptr = None
-        self.stats_ptr = None
+
+    def stats_doubles(self):
+        return 5 * self.groups * self.C + 2
 
     def _args(self):
         ign, act, sq, batch, bg, mode, smooth, alpha, beta, focal, gamma = self.settings
         return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(ign), int(act), int(sq), int(batch), int(bg), int(mode),
                 C.c_float(smooth), C.c_float(alpha), C.c_float(beta), int(focal), C.c_float(gamma), C.c_void_p(self.weight_ptr))
 
-    def evaluate(self):
-        if self.out_ptr is not None:
-            return
-        dev = self.dev
-        out = dev.arena.alloc((2 + self.C) * 4)
-        stats = dev.arena.alloc((5 * self.groups * self.C + 2) * 8)
-        dev.call("msk_region_loss_fwd", *self._args(), C.c_void_p(out), C.c_void_p(stats))
-        self.out_ptr, self.stats_ptr = out, stats
+    def _forward(self):
+        self.dev.call("msk_region_loss_fwd", *self._args(), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
 
-    def backward(self, coef_f: float, coef_r: float, dz: Tensor | None = None) -> Tensor:
-        """coef_f dL_f/dlogits + coef_r dL_r/dlogits written into a new tensor, or added into `dz` (the CE / Dice gradient of
-        the same logits)."""
-        self.evaluate()
-        accumulate = dz is not None
-        if dz is None:
-            dz = self.logits.empty_like()
+    def _backward(self, coef_f, coef_r, accumulate, dz):
         self.dev.call("msk_region_loss_bwd", *self._args(), C.c_void_p(self.stats_ptr), C.c_float(coef_f), C.c_float(coef_r),
-                      int(accumulate), dz.msk())
-        self.logits.grad = dz
-        self.logits.grad_written = True
-        return dz
+                      accumulate, dz.msk())
 
 
-def region_node_for(logits: Tensor, labels, settings, weight_ptr=None) -> RegionNode:
-    """The node of (logits, labels, settings): two region losses on one logits tensor share it (one forward and one backward
-    pass) only if every setting agrees."""
+_CACHE = {}     # kind -> {key: node}
+
+
+def node_for(kind, logits: Tensor, labels, settings=()):
+    """The node of class `kind` for (logits, labels, settings); a second loss with the same three shares it, and with it the
+    forward and the backward pass.  More than 8 nodes of a kind empty that kind's cache alone: the four heads of a
+    deep-supervision model scored by two kinds of node stay cached through their step."""
     labels = label_for(logits, labels)
     settings = tuple(settings)
-    key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape), settings, weight_ptr)
-    node = _REGION_CACHE.get(key)
+    key = (id(logits), logits.ptr, logits.gen, labels.ptr, tuple(labels.shape)) + settings
+    cache = _CACHE.setdefault(kind, {})
+    node = cache.get(key)
     if node is None or node.logits is not logits:
-        if len(_REGION_CACHE) > 8:
-            _REGION_CACHE.clear()
-        node = RegionNode(logits, labels, settings, weight_ptr)
-        _REGION_CACHE[key] = node
+        if len(cache) > 8:
+            cache.clear()
+        node = cache[key] = kind(logits, labels, settings)
     return node
 
 
-_REGION_CACHE = {}
-
-# which float of a node's out record a term reads
-TERM_SLOT = {"ce": 0, "dice": 1, "bce": 0}
-
-
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (LossNode | RegionNode, 'ce'|'dice') or (BCENode, 'bce').  Values stay on
-    the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
+    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce'): the float node.slot(which) of the node's
+    record.  Values stay on the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 
     def __init__(self, terms):
@@ -273,7 +255,7 @@ class Scalar:
         for c, node, which in self.terms:
             node.evaluate()
             v = node.dev.d2h(node.out_ptr, (2,), np.float32)
-            tot += c * float(v[TERM_SLOT[which]])
+            tot += c * float(v[node.slot(which)])
         return tot
 
     def numpy(self):
@@ -285,29 +267,19 @@ class Scalar:
     __float__ = value
 
     def backward(self):
-        # coefficients per node, the nodes grouped per logits tensor: the CE / Dice node writes dL/dlogits, every BCE or
-        # region node on the same logits adds into it (or writes it when it is the first)
+        # coefficients per node and slot, the nodes grouped per logits tensor in term order
         per_logits = {}
         for c, node, which in self.terms:
             group = per_logits.setdefault(id(node.logits), {})
-            g = group.setdefault(id(node), [node, 0.0, 0.0])
-            if which == "dice":
-                g[2] += c
-            else:
-                g[1] += c
-        # dL/dlogits per evaluated output, then ONE backward per producing model: a
-        # multi-output model (VNetDeepSup.num_outputs = 4) receives the list in forward order
+            group.setdefault(id(node), [node, 0.0, 0.0])[1 + node.slot(which)] += c
+        # dL/dlogits per evaluated output: the node that writes it first, every other node of the same logits adds into it
+        # (or writes it when it is the first).  Then ONE backward per producing model: a multi-output model
+        # (VNetDeepSup.num_outputs = 4) receives the list in forward order
         producers = {}
         for group in per_logits.values():
             dz = None
-            for node, cce, cdice in group.values():
-                if isinstance(node, LossNode):
-                    dz = node.backward(cce, cdice)
-            for node, coef, cdice in group.values():
-                if isinstance(node, BCENode):
-                    dz = node.backward(coef, dz)
-                elif isinstance(node, RegionNode):
-                    dz = node.backward(coef, cdice, dz)
+            for node, coef_a, coef_b in sorted(group.values(), key=lambda g: not g[0].writes):
+                dz = node.backward(coef_a, coef_b, None if node.writes else dz)
             logits = next(iter(group.values()))[0].logits
             prod = logits.producer
             if prod is not None:

@@ -10,7 +10,8 @@ import numpy as np
 
 from ... import nn
 from ...cvlibs import manager
-from .fused import (REGION_ACTIVATIONS, REGION_DICE, REGION_TVERSKY, Scalar, per_channel_dice, region_node_for)
+from .fused import REGION_ACTIVATIONS, REGION_DICE, REGION_TVERSKY, RegionNode, Scalar, node_for, per_channel_dice
+from .loss_utils import device_weights
 
 
 def _check_gamma(gamma):
@@ -52,14 +53,11 @@ class _RegionLoss(nn.Layer):
         if self.weight is not None:
             if self.weight.size != logits.c:
                 raise ValueError("%s weight has %d entries for %d classes" % (type(self).__name__, self.weight.size, logits.c))
-            if self._weight_dev is None or self._weight_dev[0] is not logits.dev:
-                ptr = logits.dev.malloc(max(self.weight.size, 4) * 4)
-                logits.dev.h2d(ptr, self.weight)
-                self._weight_dev = (logits.dev, ptr)
+            self._weight_dev = device_weights(logits.dev, self.weight, self._weight_dev)
             weight_ptr = self._weight_dev[1]
         settings = (self.ignore_index, REGION_ACTIVATIONS[self.activation], int(self.squared_pred), int(self.batch_dice),
                     int(self.do_bg), self._mode, self.smooth, self.alpha, self.beta, int(self._focal_on), self.gamma)
-        return region_node_for(logits, labels, settings, weight_ptr)
+        return node_for(RegionNode, logits, labels, settings + (weight_ptr,))
 
 
 @manager.LOSSES.add_component

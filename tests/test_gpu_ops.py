@@ -508,7 +508,9 @@ def test_adam():
 
 
 @pytest.mark.parametrize("sigmoid_norm,weighted", [(False, False), (True, True), (False, True)])
-@pytest.mark.parametrize("ncls,shape", [(3, (2, 5, 6, 7)), (2, (1, 4, 8, 9)), (5, (1, 3, 4, 5))])
+# (8 and 20 classes on 273 voxels: the quad-tile form, one full tile of 256 voxels and a ragged one of 17)
+@pytest.mark.parametrize("ncls,shape", [(3, (2, 5, 6, 7)), (2, (1, 4, 8, 9)), (5, (1, 3, 4, 5)), (8, (1, 3, 7, 13)),
+                                        (20, (1, 3, 7, 13))])
 def test_dice_options(ncls, shape, sigmoid_norm, weighted):
     """DiceLoss(sigmoid_norm=False) and DiceLoss(weight=...) (dice_loss.py:36-43,68-69) through msk_loss_fwd_ex /
     msk_loss_bwd_ex against the float64 oracle; the CE term beside it is unchanged."""
@@ -1220,6 +1222,36 @@ def test_tile_staged_records_equal_the_direct_form_bitwise():
         assert np.array_equal(a, b_)
     ref = O.conv3d(z.astype(np.float64), w.astype(np.float64), b.astype(np.float64), (1, 1, 1), (0, 0, 0))
     assert rel_err(res[1][0], ref) < 1e-5
+
+    # second round: the softmax-normalised Dice with a weight vector (msk_loss_fwd_ex / msk_loss_bwd_ex) through the tiles
+    def ex_round(ncls, shape, staging):
+        N, D, H, W = shape
+        rng = np.random.default_rng(100 + ncls)
+        zt = t_from_ncdhw((rng.standard_normal((N, ncls, D, H, W)) * 2).astype(np.float32))
+        y = rng.integers(0, ncls, (N, D, H, W)).astype(np.int32)
+        yp = dmalloc(y.nbytes)
+        d.h2d(yp, y)
+        wv, dwp = vec(rng.uniform(0.5, 2.0, ncls)), vec(rng.uniform(0.5, 2.0, ncls))
+        out, stats = vec(np.zeros(2 + ncls)), dmalloc((3 * ncls + 2) * 8)
+        dz = t_empty(N, ncls, D, H, W, fill=9.0)
+        try:
+            d.set_option("tile_staging", staging)
+            d.call("msk_loss_fwd_ex", zt.msk(), vp(yp), vp(wv), 255, 1, vp(dwp), vp(out), vp(stats))
+            d.call("msk_loss_bwd_ex", zt.msk(), vp(yp), vp(wv), 255, 1, vp(dwp), vp(stats), C.c_float(0.7), C.c_float(1.3),
+                   dz.msk())
+        finally:
+            d.set_option("tile_staging", 7)
+        return vec_back(out, 2 + ncls), dz.numpy()
+
+    for ncls_, shape in ((20, (N, D, H, W)), (8, (1, 3, 7, 13))):      # quad tiles against a lane's own loads
+        (o1, g1), (o0, g0) = ex_round(ncls_, shape, 7), ex_round(ncls_, shape, 0)
+        assert np.array_equal(o1, o0) and np.array_equal(g1, g0), ncls_
+    # 3 classes: without bit 2 the lane-per-class kernels run, whose sums are ordered differently: the flat tile's results stay
+    # within the tolerances of test_dice_options
+    (o1, g1), (o0, g0) = ex_round(3, (1, 3, 7, 13), 7), ex_round(3, (1, 3, 7, 13), 3)
+    assert abs(o1[0] - o0[0]) < 2e-5 * abs(o0[0])
+    assert abs(o1[1] - o0[1]) < 2e-6 and rel_err(o1[2:], o0[2:]) < 2e-6
+    assert rel_err(g1, g0) < 5e-6
 
 
 def test_small_pack_cache_follows_every_weight_write():

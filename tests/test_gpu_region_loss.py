@@ -83,6 +83,44 @@ def _combos(Cn):
         yield "sigmoid", sq, batch, bg, tv, 0, 0.0, False
 
 
+@pytest.mark.parametrize("batch", [1, 0])
+@pytest.mark.parametrize("Cn", [3, 8, 20])
+def test_region_kernels_give_the_same_bits_dense_and_as_a_view(Cn, batch):
+    """A dense tensor travels through the LDS tiles (flat at 3 classes with batch_dice, quads at 8 and 20), a channel slice of a
+    wider buffer (ld = C + 4) through a lane's own loads and stores.  The voxel of a thread, the plan and the arithmetic per
+    voxel are the same in both forms, so the record, the statistics and the gradient are the same bits.  (3 classes per
+    sample: a group of 945 floats is not quad-aligned, both layouts take the lane's own loads.)  315 voxels per sample: one full
+    tile of 256 and a ragged one of 59."""
+    d = dev()
+    shape = N, D, H, W = (2, 5, 7, 9)
+    rng = np.random.default_rng(500 + Cn)
+    z, y = _data(rng, shape, Cn)
+    yp = _device_labels(y)
+    wp = vec(rng.uniform(0.5, 2, Cn).astype(np.float32))
+    G = 1 if batch else N
+    settings = _settings("softmax", 0, batch, 0, None, 1, 2.0)
+    c0, wide = 2, Cn + 4
+    zw = rng.standard_normal((N, wide, D, H, W)).astype(np.float32)
+    zw[:, c0:c0 + Cn] = z
+    base = rng.standard_normal((N, wide, D, H, W)).astype(np.float32)
+    got = {}
+    for layout in ("dense", "view"):
+        zt = t_from_ncdhw(zw).channel_slice(c0, c0 + Cn) if layout == "view" else t_from_ncdhw(z)
+        out, stats = _fwd(zt, yp, settings, wp, G)
+        res = [out, d.d2h(stats, (5 * G * Cn + 2,), np.float64)]
+        for acc in (0, 1):
+            dw = t_from_ncdhw(base if layout == "view" else base[:, c0:c0 + Cn])
+            dt = dw.channel_slice(c0, c0 + Cn) if layout == "view" else dw
+            d.call("msk_region_loss_bwd", zt.msk(), vp(yp), *settings, vp(wp), vp(stats), C.c_float(0.75), C.c_float(1.25), acc,
+                   dt.msk())
+            g = dw.numpy()
+            res.append(g[:, c0:c0 + Cn] if layout == "view" else g)
+        got[layout] = res
+    for what, a, b in zip(("out", "stats", "gradient", "gradient added"), got["dense"], got["view"]):
+        assert np.array_equal(a, b), what
+    assert np.abs(got["dense"][2]).max() > 0 and np.isfinite(got["dense"][0]).all()
+
+
 @pytest.mark.parametrize("layout", ["dense", "dense_acc", "slice", "slice_acc"])
 @pytest.mark.parametrize("shape", [(1, 5, 7, 9), (3, 5, 7, 9), (2, 9, 16, 17), (2, 16, 16, 16)])
 @pytest.mark.parametrize("Cn", [1, 2, 3, 4, 8, 20, 33])

@@ -3,60 +3,20 @@ loss_computation and Scalar.backward through the real host stack over a stand-in
 tests/fake_msegk_region.c; numbers are garbage by construction, nothing numeric is asserted)."""
 import ctypes as C
 import os
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
+
+import fake_lib
+from fake_lib import calls, fake as _fake  # noqa: F401  (calls is a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 DICECE_YML = os.path.join(ROOT, "configs", "synthetic", "vnet_synthetic_ct_patch_dicece_96.yml")
 
 
-@pytest.fixture(scope="module")
-def fake_pkg(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("fake") / "libfake_msegk_region.so")
-    subprocess.check_call(["gcc", "-shared", "-fPIC", "-O1", "-w", "-o", so, os.path.join(HERE, "fake_msegk.c"),
-                           os.path.join(HERE, "fake_msegk_region.c")])
-    for m in [k for k in sys.modules if k.startswith("medicalseg_amd")]:
-        del sys.modules[m]
-    import importlib
-    lib = importlib.import_module("medicalseg_amd._lib")
-    real = lib.LIB_PATH
-    lib.LIB_PATH = so
-    lib._lib = None
-    import medicalseg_amd
-    from medicalseg_amd.device import Device
-    Device._current = None
-    yield medicalseg_amd
-    lib.LIB_PATH = real
-    lib._lib = None
-    Device._current = None
-    for m in [k for k in sys.modules if k.startswith("medicalseg_amd")]:
-        del sys.modules[m]
-
-
-@pytest.fixture
-def calls(fake_pkg, monkeypatch):
-    """names of the library calls made through Device.call, in order"""
-    from medicalseg_amd.device import Device
-    names = []
-    real = Device.call
-
-    def recording(self, name, *args):
-        names.append(name)
-        return real(self, name, *args)
-    monkeypatch.setattr(Device, "call", recording)
-    return names
-
-
-def _fake(name, restype, *args):
-    from medicalseg_amd import _lib
-    fn = getattr(_lib.load(), name)
-    fn.restype = restype
-    return fn(*args)
+fake_pkg = fake_lib.fake_pkg_fixture("fake_msegk.c", "fake_msegk_region.c")
 
 
 def _region_calls():
