@@ -77,6 +77,8 @@ struct msk_ctx {
   void* spack = nullptr;      // packed-weight cache of the other convolution kernels (msk_conv.hip: SmallPackCache)
   int wbf_pack_lds = 1;       // option "wbf_pack_lds": packed Winograd weights through an LDS tile with whole-run loads and 16-byte stores (wbf_pack_weights_lds_k); 0 = one thread per element (A/B)
   int wbf_bpf = 1;            // option "wbf_bpf": weight-fragment prefetch depth of wbf_gemm_k: 1 (default), 4 = four taps ahead, 0 = 4 for launches of <= 8 workgroups per CU (round 5 A/B: 18.45 ms with 1, 18.58 with 0 / 4 -- the deeper ring costs more than the waits it removes)
+  int wbf_fused_sh = 1;       // option "wbf_fused_sh": MFMA shape of the pipelined one-kernel matrix stage with 32 output channels: 1 = 16x16x32 over tap pairs, 0 = 32x32x16 (A/B, tests)
+  int wbf_gemm_form = -1;     // option "wbf_gemm_form": LDS stage depth / MFMA shape of wbf_gemm_k (-1 = pick_gemm_form; 0 / 2 = force: A/B, tests)
   int wbf_ks_blocks = 2;      // option "wbf_ks_blocks": workgroups per CU the split-K of wbf_gemm_k aims for (deep levels; every slab is a round trip of M through HBM)
   int noop_after_merge = 0;   // debug option "noop_after_merge": that many empty launches behind every merge kernel (what a 5-us launch costs the step)
   int wgrad_c1_wpc = 2;       // option "wgrad_c1_wpc": persistent workgroups per CU of wgrad_c1_mfma_k (LDS allows 3)

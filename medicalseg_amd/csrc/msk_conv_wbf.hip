@@ -9,7 +9,11 @@
 //                    NP = 1: one fp16 value (option "conv_fp16": the fp16 path of BASELINE configs[3], UNet3D);
 //   2. wbf_gemm_k  for each Winograd point xi an independent 2-D (kd, kh) convolution
 //                      M_xi[n,d,h,t][co] = sum_{kd,kh,ci} V_xi[n,d+kd-p,h+kh-p,t][ci] * U_xi[kd,kh][ci][co]
-//                  as an implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16}; NP = 3: SIX products per fp32 product
+//                  as an implicit GEMM on the 16-bit matrix pipe.  MFMA shapes: v_mfma_f32_16x16x32_f16 on the product path
+//                  (fp16 x 2 pieces, K = 5) -- wbf_gemm_k with >= 64 output channels over two-chunk LDS stages, the pipelined
+//                  wbf_gemm_fused_k with 32 output channels over tap pairs: where the chip holds its clock down under load it
+//                  holds a higher one on this shape (profiles/r21_gemm_forms.txt) -- and v_mfma_f32_32x32x16_{bf16,f16}
+//                  everywhere else (64-channel one-kernel class, bf16 x 3, K = 3, odd chunk counts); NP = 3: SIX products per fp32 product
 //                      hi*hi + hi*mid + mid*hi + mid*mid + hi*lo + lo*hi      (fp32 accumulate)
 //                  -- the dropped terms (mid*lo, lo*mid, lo*lo) are <= 2^-23 of |V||U|, the size of one fp32 rounding;
 //                  the transformed weights U = G w are computed in double and split the same way.  The 16-bit pipe runs
@@ -757,6 +761,19 @@ __device__ __forceinline__ void frag_pos(int r, int& a, int& b) {
   }
 }
 
+// The same for the 16-position sub-fragments of the 16x16x32 form (SH = 16): sub-fragment g of the tile, row r (0..15) ->
+// (d, h).  A ds_read_b128 of this form has lanes 0-15 / 16-31 (32-47 / 48-63) on DIFFERENT planes (khalf, chunk) of the image
+// with the same 16 positions, and every plane starts on a multiple of 16 slots (NSLOT = 240, 400, 144, 720), so each lane
+// group of the rule above holds every row r exactly once: the 16 positions of a sub-fragment must be distinct modulo 16.
+// TH = 16 / 32: 16 consecutive slots of one tile row.  TH = 8 (pitch 12): rows a and a + 2, 24 slots apart -> 0-7 and 8-15.
+template <int TH>
+__device__ __forceinline__ void subfrag_pos(int g, int r, int& d, int& h) {
+  if (TH == 8) { d = (g >> 1) * 4 + (g & 1) + 2 * (r >> 3); h = r & 7; }
+  else { d = g / (TH / 16); h = (g % (TH / 16)) * 16 + r; }
+}
+#define WBF_MFMA16_H(acc, wv, av) \
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wv), __builtin_bit_cast(f16x8, av), acc, 0, 0, 0)
+
 // Workgroup = 4 wavefronts as WM (rows) x WN (column groups of 32); a wavefront owns MR row fragments of 32 positions
 // and ONE 32-channel column fragment: its B fragments come straight from L2/L1 (NP slots per tap and 16-channel chunk,
 // used by MR*6 (or MR) MFMAs), A fragments from the LDS halo tile (TD+K-1) x (TH+K-1) that the whole workgroup shares
@@ -765,13 +782,25 @@ __device__ __forceinline__ void frag_pos(int r, int& a, int& b) {
 // instructions between a request and its use -- an L2 round trip is several times that -- which the big launches hide behind
 // three or four resident workgroups per CU; the deep levels (<= 2048 workgroups of one or two chunks each) run one or two
 // per CU and waited on every tap.  BPF = 4: a ring of five fragment sets (+24 registers).
-template <int MR, int WM, int WN, int TD, int TH, int K, int NP, int BPF = 1>
+// SH = 16 (NP = 2, K = 5, an even slab [kc0, kc1) only): v_mfma_f32_16x16x32_f16 on TWO-CHUNK stages.  A stage holds the halo
+// tiles of two consecutive 16-channel chunks (the planes of chunk kc + 1 follow those of kc in V, so the fill's item -> plane
+// map simply runs on) and the K = 32 of one instruction covers both: lane group kq = lane >> 4 holds (chunk kq >> 1, khalf
+// kq & 1).  Half the fill / vmcnt(0) / barrier phases per tile.  The WEIGHTS are the row operand -- two tiles of 16 channels --
+// and the wavefront's MR x 32 positions are 2 MR column tiles of 16 (subfrag_pos): a lane's four accumulator values are four
+// consecutive channels of one position, stored as one 16-byte piece; the same output tile, accumulator count, LDS and L2
+// bytes per wavefront as SH = 32.  The pipeline step is (tap, half of the sub-fragments): MR sub-fragments x 2 pieces in
+// flight, as many operand registers as one tap of SH = 32.  Where the chip holds its clock down under load the clock depends
+// on the MFMA shape: 12 % less kernel time than SH = 32 at equal matrix work in every class (profiles/r21_gemm_forms.txt).
+template <int MR, int WM, int WN, int TD, int TH, int K, int NP, int BPF = 1, int SH = 32>
 __global__ void __launch_bounds__(WM * WN * 64)
 wbf_gemm_k(GemmArgs a) {
   static_assert((WM * WN == 4 || WM * WN == 2) && WM * MR * 32 == TD * TH, "tile shape");
+  static_assert(SH == 32 || (SH == 16 && NP == 2 && BPF == 1), "stage form");
+  constexpr int CPS = SH == 16 ? 2 : 1;   // chunks per LDS stage
   constexpr int NT = WM * WN * 64;  // workgroup size: 4 wavefronts, or 2 with twice the row fragments each (half the B loads per MFMA)
   constexpr int NXI = nxi_of(K), T2 = K * K, PADK = (K - 1) / 2;
-  constexpr int HDt = TD + K - 1, HPt = TH + K - 1, NSLOT = HDt * HPt, NPL = 2 * NP, NIT = NPL * NSLOT, ROUNDS = (NIT + NT - 1) / NT;
+  constexpr int HDt = TD + K - 1, HPt = TH + K - 1, NSLOT = HDt * HPt, NPL = 2 * NP, NIT = CPS * NPL * NSLOT, ROUNDS = (NIT + NT - 1) / NT;
+  static_assert(SH == 32 || NSLOT % 16 == 0, "planes of the image start on a bank row (subfrag_pos)");
   __shared__ uint4 lds[ROUNDS * NT];
 
   const int tid = threadIdx.x;
@@ -818,6 +847,105 @@ wbf_gemm_k(GemmArgs a) {
   const unsigned uchunk = (unsigned)NP * ustep;         // bytes between 16-channel chunks
   const unsigned utap = (unsigned)a.KC * uchunk;        // bytes between taps
 
+  const int kc0 = ks * a.kc_per;
+  const int kc1 = min(a.KC, kc0 + a.kc_per);
+  if constexpr (SH == 16) {
+  constexpr int NS = 2 * MR;   // 16-position sub-fragments of this wavefront
+  const int l16 = lane & 15, kq = lane >> 4;
+  int arow[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    int dd, hh;
+    subfrag_pos<TH>(wm * NS + s, l16, dd, hh);
+    arow[s] = ((kq >> 1) * NPL + (kq & 1)) * NSLOT + dd * HPt + hh;
+  }
+  const unsigned ulane16 = (unsigned)((kq & 1) * a.CN + (grp * WN + wn) * 32 + l16) * 16u + (unsigned)(kq >> 1) * uchunk;
+  f32x4 acc[NS][2];   // [sub-fragment][16-channel tile]
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) acc[s][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int kc = kc0; kc < kc1; kc += 2) {
+    __syncthreads();  // every wavefront is done reading the previous stage's tiles
+    const unsigned vsoff = (unsigned)(kc * NPL * a.v_plane);
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(vres, (__attribute__((address_space(3))) void*)(lds + r * NT + wave * 64), 16,
+                                               (int)voff[r], (int)vsoff, 0, 0);
+    const unsigned ukc = (unsigned)kc * uchunk;
+    uint4 bq[2][2][NP];   // weight fragments [tap & 1][channel tile][piece], one tap ahead
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) bq[0][ct][p] = buf_load16(ures, ulane16 + ct * 256u, ukc + p * ustep);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // pipeline step = (tap, half): the position fragments of the NEXT step are read while this one multiplies
+    uint4 aq[2][MR][NP];
+    uint4 bdown[2];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      const uint4* ap = lds + arow[m];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) aq[0][m][p] = ap[p * 2 * NSLOT];
+    }
+#pragma unroll
+    for (int it = 0; it < 2 * T2; ++it) {
+      const int tap = it >> 1, half = it & 1, cur = it & 1, nx = cur ^ 1, bcur = tap & 1;
+      if (half == 0 && tap + 1 < T2) {
+        const unsigned ub = (unsigned)(tap + 1) * utap + ukc;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) bq[bcur ^ 1][ct][p] = buf_load16(ures, ulane16 + ct * 256u, ub + p * ustep);
+      }
+      if (it + 1 < 2 * T2) {
+        const int t1 = (it + 1) >> 1, h1 = (it + 1) & 1;
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+          const uint4* ap = lds + arow[h1 * MR + m] + (t1 / K) * HPt + (t1 % K);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) aq[nx][m][p] = ap[p * 2 * NSLOT];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // small terms first, as SH = 32: lo * (hi * 2^-11), hi * lo, hi * hi
+      if (half == 0) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) bdown[ct] = wbf_hi_down(bq[bcur][ct][0]);
+      }
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc[half * MR + m][ct], bdown[ct], aq[cur][m][NP - 1]);
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc[half * MR + m][ct], bq[bcur][ct][NP - 1], aq[cur][m][0]);
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc[half * MR + m][ct], bq[bcur][ct][0], aq[cur][m][0]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // store M[ks][xi][n][t][d][h][co]: lane (kq, position) holds channels 4 kq .. 4 kq + 3 of each 16-channel tile -- the four
+  // lane groups write 64 consecutive bytes per position and tile, the two tiles complete the position's 128-byte line
+  float* mbase = a.M + ((long)ks * NXI + xi) * a.m_xi + ((long)(n * a.T + t) * a.LD) * a.LH * a.CN + (grp * WN + wn) * 32 + 4 * kq;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    int dd, hh;
+    subfrag_pos<TH>(wm * NS + s, l16, dd, hh);
+    const int d = tdi * TD + dd, h = thi * TH + hh;
+    if (d < a.LD && h < a.LH) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) *(f32x4*)(mbase + ((long)d * a.LH + h) * a.CN + ct * 16) = acc[s][ct];
+    }
+  }
+  } else {
   // A rows of this lane: fragment f = wm*MR + mr covers tile rows [32 f, 32 f + 32), row -> (dd, hh) = (r / TH, r % TH)
   int arow[MR];
 #pragma unroll
@@ -833,8 +961,6 @@ wbf_gemm_k(GemmArgs a) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[mr][j] = 0.f;
 
-  const int kc0 = ks * a.kc_per;
-  const int kc1 = min(a.KC, kc0 + a.kc_per);
   for (int kc = kc0; kc < kc1; ++kc) {
     __syncthreads();  // every wavefront is done reading the previous chunk's tile
     const unsigned vsoff = (unsigned)(kc * NPL * a.v_plane);
@@ -929,6 +1055,7 @@ wbf_gemm_k(GemmArgs a) {
       if (d < a.LD && h < a.LH) mbase[((long)d * a.LH + h) * a.CN] = acc[mr][j];
     }
   }
+  }  // SH
   }  // tiles of this workgroup
 }
 
@@ -1008,10 +1135,18 @@ __device__ __forceinline__ void at_column(int xi, float& c0, float& c1, float& c
 // not the latency.  The tap loop is then LDS -> MFMA only (ds_read_b128 at 256 B/clk/CU: A + B reads = half of that at the
 // full matrix rate).  LDS: 25 KB tile + 50 KB weights per workgroup (exact sizes: the last fill round is wave-granular), two
 // workgroups per CU = 150 of 160 KB.
-template <int MR, int WM, int WN, int TD, int TH, int K, int NP, bool STATS, int BPF = (NP == 2 ? WBF_FUSED_BPF : 1), int BL = 0>
+// SH = 16 (pipelined form, one column fragment): v_mfma_f32_16x16x32_f16.  The LDS budget leaves no room for two chunks per
+// stage, so the K = 32 of one instruction is TWO TAPS x one 16-channel chunk: lane group kq = lane >> 4 holds (tap kq >> 1 of
+// the pair, khalf kq & 1).  Pairs stay inside a phase (6/6/6/7 taps -> 3/3/3/3.5 pairs); the 25th tap runs with a zero upper-K
+// half (13 pair slots for 12.5: 4 % more matrix work).  The fills, the counted waits, the barriers and the LDS image are those
+// of SH = 32; the lane addresses of the ds_read_b128s, the tap loop, the AT fold and the epilogue follow the 16 x 16 tile map
+// (positions = rows in subfrag_pos order, channels = columns: a lane owns channels l16 and 16 + l16).
+template <int MR, int WM, int WN, int TD, int TH, int K, int NP, bool STATS, int BPF = (NP == 2 ? WBF_FUSED_BPF : 1), int BL = 0, int SH = 32>
 __global__ void __launch_bounds__(WM * WN * 64, 2)
 wbf_gemm_fused_k(FusedArgs f) {
   static_assert(WM * WN == 4 && WM * MR * 32 == TD * TH, "tile shape");
+  static_assert(SH == 32 || (SH == 16 && BL == 2 && WN == 1 && NP == 2), "16x16x32: pipelined form, one column fragment");
+  constexpr int NS16 = 2 * MR;   // SH = 16: 16-position sub-fragments of a wavefront
   const GemmArgs& a = f.g;
   constexpr int NT = WM * WN * 64;
   constexpr int NXI = nxi_of(K), T2 = K * K, PADK = (K - 1) / 2;
@@ -1075,6 +1210,14 @@ wbf_gemm_fused_k(FusedArgs f) {
     for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
       for (int j = 0; j < 16; ++j) yo[i][mr][j] = 0.f;
+  f32x4 yo16[4][NS16][2];   // SH = 16: [W output][sub-fragment][16-channel tile]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int s = 0; s < NS16; ++s)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) yo16[i][s][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int l16 = lane & 15, kq = lane >> 4;
 
   if constexpr (BL == 2) {
     // ---- pipelined form (round 6): nothing the tap loop reads is waited for where it is requested ------------------------
@@ -1169,8 +1312,112 @@ wbf_gemm_fused_k(FusedArgs f) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
+    // SH = 16: the same phase -- waits, barrier and fills word for word -- with the taps in pairs
+    f32x4 acc16[NS16][2];
+    int arow16[NS16], abase16[NS16];
+#pragma unroll
+    for (int s = 0; s < NS16; ++s) {
+      int dd, hh;
+      subfrag_pos<TH>(wm * NS16 + s, l16, dd, hh);
+      arow16[s] = (kq & 1) * NSLOT + dd * HPt + hh;
+    }
+    auto run_phase16 = [&](int s_, auto qc) {
+      constexpr int q = decltype(qc)::value;
+      constexpr int T0 = PQ_T[q], T1 = PQ_T[q + 1], NPAIR = (T1 - T0 + 1) / 2;
+      const bool more = s_ + 1 < NS;
+      if (q == 1 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ROUNDS) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if constexpr (q < PH - 1) fill_weights(s_, std::integral_constant<int, q + 1>{});
+      else if (more) fill_weights(s_ + 1, std::integral_constant<int, 0>{});
+      if (q == 0 && more) fill_tile(s_ + 1);
+      // lane (kq, l16): weights of tap (kq >> 1) of the pair, khalf kq & 1, channel ct * 16 + l16 -- slot khalf * 32 + channel of
+      // fragment (tap, piece); positions: plane khalf of the tile at the offset of ITS tap of the pair
+      const uint4* bl = lds + 2 * NIT + ((q + (s_ & PH & 1)) & 1) * PQ_SLOT + (kq & 1) * 32 + l16;
+      const uint4* blk = bl + (kq >> 1) * NP * 64;
+      const bool up = (kq >> 1) != 0;
+      uint4 aq[2][NP], bq[2][2][NP], bdown[2];
+      auto load_b = [&](int j, uint4 (&d_)[2][NP]) {
+        const bool full = T0 + 2 * j + 1 < T1;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            if (full) {
+              d_[ct][p] = blk[(2 * j * NP + p) * 64 + ct * 16];
+            } else {   // the 25th tap alone: the upper-K lanes multiply by zero (and read what the lower ones read: a valid slot)
+              const uint4 v = bl[(2 * j * NP + p) * 64 + ct * 16];
+              d_[ct][p] = up ? uint4{0u, 0u, 0u, 0u} : v;
+            }
+          }
+      };
+      auto load_a = [&](int j, int sf, uint4 (&d_)[NP]) {
+        const int t0 = T0 + 2 * j, t1 = t0 + 1 < T1 ? t0 + 1 : t0;
+        const int off = up ? (t1 / K) * HPt + (t1 % K) : (t0 / K) * HPt + (t0 % K);
+        const uint4* ap = lds + abase16[sf] + off;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) d_[p] = ap[p * 2 * NSLOT];
+      };
+      // pipeline step = (tap pair, sub-fragment): one sub-fragment's two pieces in flight keeps the kernel inside 256 registers
+      // with the weights of two pairs resident; the next pair's weights are read during the first step of this one
+      load_b(0, bq[0]);
+      load_a(0, 0, aq[0]);
+#pragma unroll
+      for (int it = 0; it < NS16 * NPAIR; ++it) {
+        const int j = it / NS16, sf = it % NS16, cur = it & 1, nx = cur ^ 1, bcur = j & 1;
+        if (sf == 0 && j + 1 < NPAIR) load_b(j + 1, bq[bcur ^ 1]);
+        if (it + 1 < NS16 * NPAIR) load_a((it + 1) / NS16, (it + 1) % NS16, aq[nx]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (sf == 0) {
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) bdown[ct] = wbf_hi_down(bq[bcur][ct][0]);  // partner of the scaled low piece (msk_wbf.h)
+        }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc16[sf][ct], aq[cur][NP - 1], bdown[ct]);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc16[sf][ct], aq[cur][0], bq[bcur][ct][NP - 1]);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) WBF_MFMA16_H(acc16[sf][ct], aq[cur][0], bq[bcur][ct][0]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
     fill_weights(0, std::integral_constant<int, 0>{});
     fill_tile(0);
+    if constexpr (SH == 16) {
+#pragma unroll 1
+    for (int s_ = 0; s_ < NS; ++s_) {
+      const int xi = s_ / a.KC, kc = s_ - xi * a.KC;
+      if (kc == 0) {
+#pragma unroll
+        for (int s = 0; s < NS16; ++s)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) acc16[s][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int s = 0; s < NS16; ++s) abase16[s] = arow16[s] + (s_ & 1) * NIT;
+      run_phase16(s_, std::integral_constant<int, 0>{});
+      run_phase16(s_, std::integral_constant<int, 1>{});
+      run_phase16(s_, std::integral_constant<int, 2>{});
+      run_phase16(s_, std::integral_constant<int, 3>{});
+      if (kc == a.KC - 1) {
+        float c0, c1, c2, c3;
+        at_column<K>(xi, c0, c1, c2, c3);
+#pragma unroll
+        for (int s = 0; s < NS16; ++s)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float m = acc16[s][ct][j];
+              yo16[0][s][ct][j] = fmaf(c0, m, yo16[0][s][ct][j]);
+              yo16[1][s][ct][j] = fmaf(c1, m, yo16[1][s][ct][j]);
+              yo16[2][s][ct][j] = fmaf(c2, m, yo16[2][s][ct][j]);
+              yo16[3][s][ct][j] = fmaf(c3, m, yo16[3][s][ct][j]);
+            }
+      }
+    }
+    } else {
 #pragma unroll 1
     for (int s_ = 0; s_ < NS; ++s_) {
       const int xi = s_ / a.KC, kc = s_ - xi * a.KC;
@@ -1202,6 +1449,7 @@ wbf_gemm_fused_k(FusedArgs f) {
           }
       }
     }
+    }  // SH
     __syncthreads();   // (nothing is in flight any more: the statistics epilogue reuses the LDS)
   } else {
 #pragma unroll 1
@@ -1392,6 +1640,114 @@ wbf_gemm_fused_k(FusedArgs f) {
   }
 
   }  // BL != 2
+  if constexpr (SH == 16) {
+    // epilogue of the 16 x 16 tile map: a lane owns TWO output channels (l16 and 16 + l16) and, of each, NS16 x 4 positions
+    // (rows 4 kq .. 4 kq + 3 of every sub-fragment) x 4 W outputs
+    const float osc = f.scaled ? 1.f / (wbf_scale_of(f.in_amax) * wbf_scale_of(f.w_amax)) : 1.f;
+    const long vox0 = ((long)n * f.dvn + (long)(4 * t) * f.dvw) * f.dld;
+    const long wst = (long)f.dvw * f.dld;
+    const bool split_st = f.st_lo != nullptr;
+    const long swst = split_st ? (wst >> 1) : wst;
+    const long aoff = f.acc_src ? (f.acc_src - f.dst) : 0;
+    const int wlim = f.LW - 4 * t;
+    WfRec rec[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const int co = ct * 16 + l16;
+      const float bv = f.bias ? f.bias[co] : 0.f;
+      const float sl = f.prelu ? f.prelu[co] : 1.f;
+      float* obase = f.dst + vox0 + co;
+      float* sbase = split_st ? (co < f.csplit ? f.st_lo + co : f.st_hi + (co - f.csplit)) + (vox0 >> 1) : obase;
+      float sk = 0.f, s1 = 0.f, s2 = 0.f, cnt = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS16; ++s) {
+        // four positions x four W outputs at a time; the accumulate path loads all 16 old values before the first store
+        float* op[4];
+        bool ok[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          int dd, hh;
+          subfrag_pos<TH>(wm * NS16 + s, 4 * kq + jj, dd, hh);
+          const int d = tdi * TD + dd, h = thi * TH + hh;
+          ok[jj] = d < a.LD && h < a.LH;
+          op[jj] = obase + ((long)d * f.dvd + (long)h * f.dvh) * f.dld;
+        }
+        float old[4][4];
+        if (f.accumulate) {
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) old[jj][i] = (ok[jj] && i < wlim) ? __builtin_nontemporal_load(op[jj] + aoff + i * wst) : 0.f;
+        }
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          if (!ok[jj]) continue;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (i >= wlim) break;
+            float r = fmaf(yo16[i][s][ct][jj], osc, bv);
+            if (f.accumulate) r += old[jj][i];
+            if (f.prelu) r = r > 0.f ? r : sl * r;
+            if (split_st) sbase[((op[jj] - obase) >> 1) + i * swst] = r;
+            else op[jj][i * wst] = r;
+            if (STATS) {
+              if (cnt == 0.f) sk = r;
+              const float dlt = r - sk;
+              s1 += dlt;
+              s2 = fmaf(dlt, dlt, s2);
+              cnt += 1.f;
+            }
+          }
+        }
+      }
+      rec[ct] = WfRec{0.f, 0.f, 0.f};
+      if (STATS && cnt > 0.f) {
+        rec[ct].n = cnt;
+        rec[ct].mean = sk + s1 / cnt;
+        rec[ct].m2 = fmaxf(s2 - s1 * s1 / cnt, 0.f);
+      }
+    }
+    if (STATS) {
+      // (n, mean, M2) per lane and channel -> the four lane groups (a fixed order) -> the WM wavefronts -> one record
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        WfRec w = rec[ct], o;
+        o.n = __shfl_xor(w.n, 16, 64);
+        o.mean = __shfl_xor(w.mean, 16, 64);
+        o.m2 = __shfl_xor(w.m2, 16, 64);
+        w = (kq & 1) == 0 ? wfrec_merge(w, o) : wfrec_merge(o, w);
+        o.n = __shfl_xor(w.n, 32, 64);
+        o.mean = __shfl_xor(w.mean, 32, 64);
+        o.m2 = __shfl_xor(w.m2, 32, 64);
+        rec[ct] = (kq & 2) == 0 ? wfrec_merge(w, o) : wfrec_merge(o, w);
+      }
+      __syncthreads();  // the last stage's LDS reads are done
+      float* sh = reinterpret_cast<float*>(lds);
+      if (kq == 0) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          float* p_ = sh + (wave * 32 + ct * 16 + l16) * 3;
+          p_[0] = rec[ct].n; p_[1] = rec[ct].mean; p_[2] = rec[ct].m2;
+        }
+      }
+      __syncthreads();
+      if (wm == 0 && kq == 0) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          WfRec r = rec[ct];
+#pragma unroll
+          for (int q = 1; q < WM; ++q) {
+            const float* p_ = sh + (q * 32 + ct * 16 + l16) * 3;
+            WfRec e = {p_[0], p_[1], p_[2]};
+            r = wfrec_merge(r, e);
+          }
+          float* g_ = f.stat_partial + ((long)tile_id * a.CN + ct * 16 + l16) * 3;
+          g_[0] = r.n; g_[1] = r.mean; g_[2] = r.m2;
+        }
+      }
+    }
+    return;
+  }
   // epilogue: y = yo / (operand scales) + bias [+ dst] [PReLU]; a lane owns ONE output channel (column li of the MFMA
   // result) and MR x 16 positions x 4 W outputs of it
   const int co = wn * 32 + li;
@@ -1653,8 +2009,25 @@ wbf_tout_k(ToutArgs a) {
   }
 }
 
+// LDS stage depth / MFMA shape of wbf_gemm_k (option "wbf_gemm_form"): 0 = one chunk per stage, 32x32x16; 2 = two chunks per
+// stage, 16x16x32.  Form 2 exists for the fp16 x 2 product path of the 5^3 layers with >= 64 output channels (the tile variants
+// with WN > 1; 32 output channels run the one-kernel form) and an even number of 16-channel chunks: in that class the split-K
+// slabs are whole chunk pairs WHATEVER the form (run_pipeline), so the forms differ in the matrix kernel alone.  Everything
+// else runs form 0.  Measured (tools/bench_conv.py --ab wbf_gemm_form=0,1,2, one process, random data, median of 7 rounds,
+// forward / data gradient, profiles/r21_gemm_forms.txt): 128ch@32^3 0.247 -> 0.217 ms, 256ch@16^3 0.124 -> 0.110,
+// 64ch@32^3 0.067 -> 0.061, 128ch@16^3 0.039 -> 0.035, 256ch@8^3 0.024 -> 0.021: form 2 wins every class.  (Form 1, two-chunk
+// stages on 32x32x16, bitwise form 0, LOST 1-5 % in every class and is gone: the halved barrier phases do not pay for the
+// longer fill ahead of the first tap.)
+template <int WN, int K, int NP>
+constexpr bool gemm_has_forms() { return K == 5 && NP == 2 && WN > 1; }
+bool gemm_pair_class(int WN, int K, int NP, int KC) { return K == 5 && NP == 2 && WN > 1 && (KC & 1) == 0; }
+int pick_gemm_form(const msk_ctx* ctx, int WN, int K, int NP, int KC) {
+  if (!gemm_pair_class(WN, K, NP, KC) || ctx->wbf_bpf != 1) return 0;   // (the deep weight ring, an A/B option, exists for form 0 only)
+  return ctx->wbf_gemm_form == 0 ? 0 : 2;
+}
+
 template <int MR, int WM, int WN, int TD, int TH, int K, int NP>
-void launch_gemm(msk_ctx* ctx, const char* tag, const GemmArgs& a, long nblk) {
+void launch_gemm(msk_ctx* ctx, const char* tag, const GemmArgs& a, long nblk, int form) {
   GemmArgs b = a;
   b.nblk = (int)nblk;
   // tiles per workgroup: keep >= ~6 workgroups per CU in the grid (tuning knob "wbf_tpb")
@@ -1665,6 +2038,12 @@ void launch_gemm(msk_ctx* ctx, const char* tag, const GemmArgs& a, long nblk) {
   b.tpb = (int)((nblk + grid - 1) / grid);
   // weight fragments four taps ahead for the launches that cannot hide an L2 round trip behind other workgroups (option "wbf_bpf":
   // 0 = by grid size, 1 / 4 = force)
+  if constexpr (gemm_has_forms<WN, K, NP>()) {
+    if (form == 2) {
+      MSK_LAUNCH_TIMED(ctx, tag, (wbf_gemm_k<MR, WM, WN, TD, TH, K, NP, 1, 16>), dim3((unsigned)grid), dim3(WM * WN * 64), 0, b);
+      return;
+    }
+  }
   const bool deep = MR == 2 && (ctx->wbf_bpf == 4 || (ctx->wbf_bpf == 0 && nblk <= 8L * ctx->num_cu));
   if constexpr (MR == 2) {
     if (deep) {
@@ -1717,17 +2096,17 @@ const Var* pick_variant(const msk_ctx* ctx, const WbfGeom& geo, int CN, int K) {
 }
 
 template <int K, int NP>
-void launch_gemm_variant(msk_ctx* ctx, const char* tag, int variant, const GemmArgs& ga, long nblk) {
+void launch_gemm_variant(msk_ctx* ctx, const char* tag, int variant, const GemmArgs& ga, long nblk, int form) {
   switch (variant) {
-    case 3: launch_gemm<2, 1, 4, 8, 8, K, NP>(ctx, tag, ga, nblk); break;
-    case 4: launch_gemm<2, 4, 1, 16, 16, K, NP>(ctx, tag, ga, nblk); break;
-    case 5: launch_gemm<2, 2, 2, 8, 16, K, NP>(ctx, tag, ga, nblk); break;
+    case 3: launch_gemm<2, 1, 4, 8, 8, K, NP>(ctx, tag, ga, nblk, form); break;
+    case 4: launch_gemm<2, 4, 1, 16, 16, K, NP>(ctx, tag, ga, nblk, form); break;
+    case 5: launch_gemm<2, 2, 2, 8, 16, K, NP>(ctx, tag, ga, nblk, form); break;
     default:
       if constexpr (K == 5) {
-        if (variant == 6) launch_gemm<4, 2, 1, 16, 16, 5, NP>(ctx, tag, ga, nblk);
-        else if (variant == 0) launch_gemm<4, 4, 1, 16, 32, 5, NP>(ctx, tag, ga, nblk);
-        else if (variant == 1) launch_gemm<4, 2, 2, 16, 16, 5, NP>(ctx, tag, ga, nblk);
-        else launch_gemm<4, 1, 4, 8, 16, 5, NP>(ctx, tag, ga, nblk);
+        if (variant == 6) launch_gemm<4, 2, 1, 16, 16, 5, NP>(ctx, tag, ga, nblk, form);
+        else if (variant == 0) launch_gemm<4, 4, 1, 16, 32, 5, NP>(ctx, tag, ga, nblk, form);
+        else if (variant == 1) launch_gemm<4, 2, 2, 16, 16, 5, NP>(ctx, tag, ga, nblk, form);
+        else launch_gemm<4, 1, 4, 8, 16, 5, NP>(ctx, tag, ga, nblk, form);
       }
       break;
   }
@@ -1905,6 +2284,11 @@ void launch_fused(msk_ctx* ctx, const char* tag, const FusedArgs& fa, bool stats
   if constexpr (WN == 1 && NP == 2 && NITc % 64 == 0) {
     // one column fragment (32 output channels): the stage's weights through LDS as well ("wbf_fused_bl": 2 = pipelined (default),
     // 1 = whole stage behind one wait, 0 = per-wavefront L1 loads)
+    if (ctx->wbf_fused_bl == 2 && fa.g.CN == 32 && ctx->wbf_fused_sh != 0) {   // pipelined fills, 16x16x32 taps in pairs ("wbf_fused_sh": 0 = 32x32x16, A/B)
+      if (stats) MSK_LAUNCH_TIMED_F(ctx, tag, fork, (wbf_gemm_fused_k<MR, WM, WN, TD, TH, K, NP, true, 1, 2, 16>), grid, dim3(WM * WN * 64), 0, fa);
+      else MSK_LAUNCH_TIMED_F(ctx, tag, fork, (wbf_gemm_fused_k<MR, WM, WN, TD, TH, K, NP, false, 1, 2, 16>), grid, dim3(WM * WN * 64), 0, fa);
+      return;
+    }
     if (ctx->wbf_fused_bl == 2 && fa.g.CN == 32) {   // pipelined fills (round 6)
       if (stats) MSK_LAUNCH_TIMED_F(ctx, tag, fork, (wbf_gemm_fused_k<MR, WM, WN, TD, TH, K, NP, true, 1, 2>), grid, dim3(WM * WN * 64), 0, fa);
       else MSK_LAUNCH_TIMED_F(ctx, tag, fork, (wbf_gemm_fused_k<MR, WM, WN, TD, TH, K, NP, false, 1, 2>), grid, dim3(WM * WN * 64), 0, fa);
@@ -1945,10 +2329,12 @@ int run_pipeline(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int 
   // split K (16-channel chunks) when the tiling alone cannot fill the chip
   const long base_blocks = (long)NXI * ngrp * tiles_h * tiles_d * T * g.N;
   int ksplit = 1, kc_per = KC;
+  const int form = pick_gemm_form(ctx, WN, K, NP, KC);
   if (base_blocks < 3L * ctx->num_cu && ctx->wbf_fuse != 2) {  // ("wbf_fuse" 2: tests force the one-kernel form, which has no split-K)
     long want = ((long)ctx->wbf_ks_blocks * ctx->num_cu + base_blocks - 1) / base_blocks;
     if (want > KC) want = KC;
     kc_per = (int)((KC + want - 1) / want);
+    if (gemm_pair_class(WN, K, NP, KC)) kc_per = (kc_per + 1) & ~1;   // two-chunk stages: every slab starts and ends on a chunk pair
     ksplit = (KC + kc_per - 1) / kc_per;
   }
   const long nblk = base_blocks * ksplit;
@@ -2058,8 +2444,10 @@ int run_pipeline(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int 
   const char* tag = NP == 3 ? "wbf_gemm_k" : (NP == 2 ? "wbf_gemm_h2_k" : "wbf_gemm_f16_k");
   if (ctx->prof && ctx->prof_shapes) {
     char buf[200];
-    snprintf(buf, sizeof(buf), "%s[ck=%d,cn=%d,n=%d,dhw=%dx%dx%d,k=%d,ks=%d%s]", tag, g.CK, g.CN, g.N, g.DD, g.DH, g.DW, K, ksplit,
-             fuse_out ? ",fused" : "");
+    // (",sh16": launch_fused's rule for the 16x16x32 pipelined form -- one column fragment, fp16 x 2 pieces, wave-granular tile)
+    const bool sh16 = fuse_out && K == 5 && NP == 2 && variant == 4 && g.CN == 32 && ctx->wbf_fused_bl == 2 && ctx->wbf_fused_sh != 0;
+    snprintf(buf, sizeof(buf), "%s[ck=%d,cn=%d,n=%d,dhw=%dx%dx%d,k=%d,ks=%d%s%s]", tag, g.CK, g.CN, g.N, g.DD, g.DH, g.DW, K, ksplit,
+             fuse_out ? (sh16 ? ",fused,sh16" : ",fused") : "", fuse_out || form == 0 ? "" : ",form=2");
     tag = msk_intern_tag(ctx, buf);
   }
   if (fuse_out) {
@@ -2100,7 +2488,7 @@ int run_pipeline(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int 
     if (g.xform) ctx->xform_written = true;
     return 1;
   }
-  launch_gemm_variant<K, NP>(ctx, tag, variant, ga, nblk);
+  launch_gemm_variant<K, NP>(ctx, tag, variant, ga, nblk, form);
   MSK_LAUNCH_CHECK(ctx);
   {
     ToutArgs oa{};

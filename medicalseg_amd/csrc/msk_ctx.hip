@@ -408,6 +408,7 @@ int msk_get_option(msk_ctx* ctx, const char* key, int* value) {
   else if (strcmp(key, "wgrad_async") == 0) *value = ctx->wgrad_async ? 1 : 0;
   else if (strcmp(key, "world") == 0) *value = ctx->world;
   else if (strcmp(key, "rank") == 0) *value = ctx->rank;
+  else if (strcmp(key, "num_cu") == 0) *value = ctx->num_cu;   // what the split-K and grid rules count in (tests evaluate them)
   // amax arrays handed out so far by the compute stream's ring / the weight-gradient stream's ring (modulo 2^30): an array is
   // zeroed again 512 requests after it was handed out -- a holder that spans a whole step (Tensor.amax: forward -> weight
   // gradient) is safe while a step stays under that (device.Arena.reset checks)
@@ -475,6 +476,14 @@ int msk_set_option(msk_ctx* ctx, const char* key, int value) {
   }
   if (strcmp(key, "wbf_bpf") == 0) {  // weight-fragment prefetch depth of wbf_gemm_k: 0 auto (by grid size), 1, 4
     ctx->wbf_bpf = value;
+    return 0;
+  }
+  if (strcmp(key, "wbf_fused_sh") == 0) {  // pipelined one-kernel matrix stage, 32 output channels: 1 (default) = 16x16x32 MFMAs over tap pairs, 0 = 32x32x16 (A/B, tests)
+    ctx->wbf_fused_sh = value != 0 ? 1 : 0;
+    return 0;
+  }
+  if (strcmp(key, "wbf_gemm_form") == 0) {  // wbf_gemm_k, fp16 x 2 pieces, >= 64 output channels: -1 auto (pick_gemm_form: 2), 0 = one chunk per LDS stage + 32x32x16 (A/B, tests), 2 = two chunks per stage + 16x16x32
+    ctx->wbf_gemm_form = value == 0 || value == 2 ? value : -1;
     return 0;
   }
   if (strcmp(key, "wbf_ks_blocks") == 0) {  // tuning: workgroups per CU targeted by the split-K of wbf_gemm_k (default 2; round 5 sweep on one box, two repetitions: 16 / 8 / 4 / 2 = 18.58 / 18.46 / 18.39 / 18.28 ms -- every slab is a round trip of M through HBM and a term of wbf_tout_k)

@@ -1,5 +1,9 @@
 """Micro-benchmark of one 'same' 5^3 convolution (forward, data gradient, weight gradient) through the C ABI,
-with the tile/chunk tuning knobs:  python tools/bench_conv.py --c 32 --size 128 --halo-tile 1 --wgrad-chunk 1"""
+with the tile/chunk tuning knobs:  python tools/bench_conv.py --c 32 --size 128 --halo-tile 1 --wgrad-chunk 1
+A/B of one option INSIDE ONE PROCESS (devices and even processes differ by more than most options do):
+    python tools/bench_conv.py --c 128 --size 32 --ab wbf_gemm_form=0,1,2
+times forward and data gradient with the listed values in turn, round after round, and prints the median and the minimum of
+every kernel tag (HIP events around each launch) per value."""
 import argparse
 import ctypes as C
 import os
@@ -8,6 +12,39 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def ab_compare(dev, a, cases, label):
+    if a.zero:
+        sys.exit("--ab times random data only: zero operands hide clock effects")
+    key, vals = a.ab.split("=")
+    vals = [int(v) for v in vals.split(",")]
+    rounds = max(5, a.rounds)
+    dev.set_option("prof_only_halo", 0)
+    for name in ("fwd", "dgrad"):
+        fn = cases[name]
+        for v in vals:   # warm-up: weight pack, workspace, code load
+            dev.set_option(key, v)
+            fn()
+        dev.sync()
+        ms = {v: {} for v in vals}   # value -> tag -> [ms per call, one per round]
+        for _ in range(rounds):
+            for v in vals:
+                dev.set_option(key, v)
+                dev.prof_reset()
+                dev.prof_enable(True)
+                for _ in range(a.iters):
+                    fn()
+                dev.sync()
+                dev.prof_enable(False)
+                for tag, (cnt, tms) in dev.prof_report().items():
+                    ms[v].setdefault(tag, []).append(tms / a.iters)
+        print(f"{label} {name}: {key} = {vals}, {rounds} rounds x {a.iters} calls, ms per call as median (min)")
+        tags = sorted({t for v in vals for t in ms[v]}, key=lambda t: -max(np.median(ms[v].get(t, [0.0])) for v in vals))
+        for tag in tags:
+            cols = "  ".join(f"{v}: {np.median(ms[v][tag]):7.4f} ({min(ms[v][tag]):7.4f})" if tag in ms[v] else f"{v}:       -          "
+                             for v in vals)
+            print(f"    {tag:28s} {cols}")
 
 
 def main():
@@ -27,6 +64,8 @@ def main():
                     "runs faster on zeros, MI355X_MICROARCH.md 'DVFS give-back')")
     ap.add_argument("--profile", action="store_true", help="also print the per-kernel HIP-event breakdown of each case")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT", help="extra msk_set_option knobs")
+    ap.add_argument("--ab", default=None, metavar="KEY=V0,V1,...", help="time these values of one option alternately in this process")
+    ap.add_argument("--rounds", type=int, default=7, help="--ab: rounds over the values (at least 5)")
     a = ap.parse_args()
     from medicalseg_amd._lib import MskConvDesc
     from medicalseg_amd.device import Tensor, get_device
@@ -58,6 +97,9 @@ def main():
         "dgrad": lambda: dev.call("msk_conv3d_dgrad", cd, dy.msk(), vp(w), dx.msk(), a.acc),
         "wgrad": lambda: dev.call("msk_conv3d_wgrad", cd, x.msk(), dy.msk(), vp(dw), vp(db), a.acc),
     }
+    if a.ab:
+        ab_compare(dev, a, cases, f"c={c}->{cn} {n}x{D}x{H}x{W} k={k}")
+        return
     for name, fn in cases.items():
         fn()
         dev.sync()
