@@ -469,6 +469,27 @@ int msk_sw_gather(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_
  * row outside its table, a window that does not intersect the volume, patches overlapping vol, acc overlapping logits.   */
 int msk_sw_accumulate(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, const float* td, int nd, const float* th, int nh,
                       const float* tw, int nw, msk_tensor acc);
+/* The two above with mirroring inside the window (nnU-Net's predictor; core/infer.py sliding_window_inference(mirror_axes=...),
+ * tests/sliding_mirror_reference.py).  A mask mirrors about the WINDOW, m_a(i) = r_a - 1 - i along every axis a whose bit is set
+ * (bit 0 = D, bit 1 = H, bit 2 = W, as msk_flip_axes), r_a the window's extent: the implicit padding is mirrored with the content.
+ * msk_sw_gather_mirrored: origins is a HOST array of patches.n x 5 int32 (n, d0, h0, w0, mask), a mask per patch;
+ *     patches[b][z][y][x][:] = P[m_D(z)][m_H(y)][m_W(x)][:],  P what msk_sw_gather writes for that origin.
+ * msk_sw_accumulate_mirrored: origins is a HOST array of logits.n x 8 int32 (n, d0, h0, w0, id, ih, iw, mask).  For the rows in
+ * order, every window voxel (z, y, x) inside the volume (volume frame, tables indexed un-mirrored) and every channel c:
+ *     w   = (td[id][z] * th[ih][y]) * tw[iw][x]
+ *     ws  = w * scale
+ *     acc = acc + (ws * logits[row][m_D(z)][m_H(y)][m_W(x)][c])
+ * in fp32 with one rounding per operation, never an FMA.  Consecutive rows whose first seven ints are equal are one window's
+ * passes: up to 8 of them are ONE launch that reads and writes the accumulator once and every pass's logits once (K + 2 window
+ * tensors instead of the 5 K of msk_flip_axes + msk_sw_accumulate per pass); the adds keep the row order, so the result is bit
+ * for bit that of one row per call.  One launch per run, in order, no atomics.  With every mask 0 (and scale == 1) the results
+ * are those of msk_sw_gather / msk_sw_accumulate bit for bit.  16 bytes per lane on the accumulator side under the conditions
+ * above; a W mirror then takes whole source quads for C == 1, C == 2 and C % 4 == 0 and four 4-byte loads for any other C (the
+ * gather: quads for D / H mirrors and for W at C == 1).  Argument errors, before any launch: those of the two above, a mask
+ * outside 0..7, a scale that is not finite and positive.                                                                  */
+int msk_sw_gather_mirrored(msk_ctx* ctx, msk_tensor vol, msk_tensor patches, const int32_t* origins, float cval);
+int msk_sw_accumulate_mirrored(msk_ctx* ctx, msk_tensor logits, const int32_t* origins, const float* td, int nd, const float* th,
+                               int nh, const float* tw, int nw, float scale, msk_tensor acc);
 
 /* ---- random patch cropping (transforms.RandomPatchCrop3D) -------------------- */
 /* Bytes of workspace msk_patch_select needs for a label volume of `voxels` voxels (in [1, 2^31)) and num_classes in

@@ -134,6 +134,8 @@ SIGNATURES = {
     "msk_tta_finish": (_i, [_vp, _T, _i, _T, _vp]),
     "msk_sw_gather": (_i, [_vp, _T, _T, _vp, _f]),
     "msk_sw_accumulate": (_i, [_vp, _T, _vp, _vp, _i, _vp, _i, _vp, _i, _T]),
+    "msk_sw_gather_mirrored": (_i, [_vp, _T, _T, _vp, _f]),
+    "msk_sw_accumulate_mirrored": (_i, [_vp, _T, _vp, _vp, _i, _vp, _i, _vp, _i, _f, _T]),
     "msk_patch_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),
     "msk_patch_select": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "msk_patch_crop": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _u32]),

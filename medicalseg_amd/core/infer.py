@@ -329,7 +329,7 @@ def sliding_release(dev):
 
 
 def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', sigma_scale=0.125, sw_batch_size=1, cval=0.0,
-                             ori_shape=None, transforms=None):
+                             ori_shape=None, transforms=None, mirror_axes=()):
     """Window-by-window prediction at native resolution: the net runs on the overlapping `roi_size` windows of SlidingPlan
     (`overlap`, implicit padding with `cval` where the volume is smaller than the window), sw_batch_size windows per forward
     (the last batch may be smaller), and the outputs are blended on the device with the plan's normalised window weights
@@ -345,9 +345,19 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
     Runs in one nn.fused_inference scope.  The plan with its device tables, the patch batch, the accumulator and (if `im`
     lives in the activation arena, which every forward resets) a copy of `im` are persistent buffers: a second call at the
     same shapes allocates no device memory, a call at other shapes frees and replaces the buffers whose shape changed (so
-    `logits` of an earlier call is gone then, as it is after the next forward); sliding_release frees them."""
+    `logits` of an earlier call is gone then, as it is after the next forward); sliding_release frees them.
+
+    mirror_axes (0/1/2 = D/H/W; nnU-Net's mirroring inside the sliding window): every window is also shown to the net mirrored
+    about the WINDOW along every subset of the axes -- the K = 1, 2, 4 or 8 masks of tta_passes(1.0, mirror_axes), mask 0
+    first -- and the mean of the K outputs, mirrored back, is what is blended (tests/sliding_mirror_reference.py).  The passes
+    are the list [(window, mask) for window in windows for mask in masks]; sw_batch_size then counts PASSES per forward, and a
+    window's passes may straddle two forwards: msk_sw_gather_mirrored -> model(patches)[0] -> one
+    msk_sw_accumulate_mirrored(scale = 1 / K) per batch.  Every pass is one add at a fixed place in the sequence, so the
+    result does not depend on sw_batch_size.  Without mirror_axes the calls are those described above, unchanged."""
     if not isinstance(sw_batch_size, (int, np.integer)) or isinstance(sw_batch_size, bool) or sw_batch_size < 1:
         raise ValueError("sliding_window_inference: sw_batch_size must be a positive integer, got %r" % (sw_batch_size,))
+    masks = [m for _, m in tta_passes(1.0, mirror_axes)]
+    mirrored = len(masks) > 1
     if not isinstance(im, Tensor):
         im = to_tensor(im)
     dev = im.dev
@@ -355,18 +365,23 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
     rd, rh, rw = plan.roi_size
     if im.gen is not None:          # an activation: the first forward would reset the arena under it
         im = _copy_into(_sw_buffer(dev, "im", im.n, im.d, im.h, im.w, im.c), im)
-    windows = plan.windows(im.n)
-    batch = min(int(sw_batch_size), len(windows))
+    work = [(wd, m) for wd in plan.windows(im.n) for m in masks]          # the passes: one per window without mirror_axes
+    batch = min(int(sw_batch_size), len(work))
     patches = _sw_buffer(dev, "patches", batch, rd, rh, rw, im.c)
     rows = [C.c_int(len(s)) for s in plan.starts]
     acc = None
     with nn.fused_inference():
-        for k in range(0, len(windows), batch):
-            group = windows[k:k + batch]
-            origins = np.array([plan.origin(wd) + wd[1:] for wd in group], np.int32)
-            corners = np.ascontiguousarray(origins[:, :4])
+        for k in range(0, len(work), batch):
+            group = work[k:k + batch]
+            origins = np.array([plan.origin(wd) + wd[1:] + (m,) for wd, m in group], np.int32)
             x = patches if len(group) == batch else Tensor(dev, patches.ptr, len(group), rd, rh, rw, im.c)
-            dev.call("msk_sw_gather", im.msk(), x.msk(), corners.ctypes.data_as(C.c_void_p), C.c_float(cval))
+            if mirrored:
+                corners = np.ascontiguousarray(origins[:, [0, 1, 2, 3, 7]])
+                dev.call("msk_sw_gather_mirrored", im.msk(), x.msk(), corners.ctypes.data_as(C.c_void_p), C.c_float(cval))
+            else:
+                origins = np.ascontiguousarray(origins[:, :7])
+                corners = np.ascontiguousarray(origins[:, :4])
+                dev.call("msk_sw_gather", im.msk(), x.msk(), corners.ctypes.data_as(C.c_void_p), C.c_float(cval))
             logit = _forward(model, x)
             if (logit.n, logit.d, logit.h, logit.w) != (len(group), rd, rh, rw):
                 raise ValueError("sliding_window_inference: the model maps a window batch of extent %r to %r; the logits "
@@ -374,6 +389,10 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
             if acc is None:
                 acc = _sw_buffer(dev, "acc", im.n, im.d, im.h, im.w, logit.c)
                 dev.memset(acc.ptr, 0, acc.voxels * acc.c * 4)
-            dev.call("msk_sw_accumulate", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
-                     C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], acc.msk())
+            if mirrored:        # the kernel finds a window's passes among the rows and adds them in one launch
+                dev.call("msk_sw_accumulate_mirrored", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
+                         C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], C.c_float(1.0 / len(masks)), acc.msk())
+            else:
+                dev.call("msk_sw_accumulate", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
+                         C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], acc.msk())
     return _finish(_restamp(acc), ori_shape, transforms)

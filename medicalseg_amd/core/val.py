@@ -46,11 +46,14 @@ def _image_info(dataset_json, idx):
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
              save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False, surface_metrics=False,
              surface_spacing=None, aug_eval=False, scales=1.0, flip_axes=(), sliding_window=None, sw_overlap=0.5,
-             sw_mode='gaussian', sw_batch_size=1):
+             sw_mode='gaussian', sw_batch_size=1, sw_mirror_axes=()):
     """sliding_window: a roi (rd, rh, rw); the logits and the prediction of every volume come from
-    ``infer.sliding_window_inference(roi_size=sliding_window, overlap=sw_overlap, mode=sw_mode, sw_batch_size=sw_batch_size)``
-    -- the net on overlapping windows at the volume's own resolution, blended on the device -- in place of the one forward of
-    ``infer.inference``; everything downstream (loss, mdice, hard and surface metrics, AUC, saved arrays) is unchanged.
+    ``infer.sliding_window_inference(roi_size=sliding_window, overlap=sw_overlap, mode=sw_mode, sw_batch_size=sw_batch_size,
+    mirror_axes=sw_mirror_axes)`` -- the net on overlapping windows at the volume's own resolution, blended on the device -- in
+    place of the one forward of ``infer.inference``; everything downstream (loss, mdice, hard and surface metrics, AUC, saved
+    arrays) is unchanged.  sw_mirror_axes (0/1/2 = D/H/W): every window is also predicted mirrored along every subset of these
+    axes and the mean of the logits is blended (nnU-Net's mirroring; sw_batch_size then counts passes); what comes back is
+    still logits.  Without sliding_window a non-empty sw_mirror_axes raises ValueError.
     Together with aug_eval it raises ValueError: combining the two is out of scope here.  The call keeps its device buffers
     (one accumulator, patch batch and plan tables per geometry; volumes of another extent replace the accumulator) after the
     loop for the next evaluation; ``infer.sliding_release(device)`` frees them.
@@ -85,6 +88,10 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
                          % (scales,))
     if sliding_window is not None and aug_eval:
         raise ValueError("evaluate: sliding_window together with aug_eval=True is not supported")
+    sw_mirror_axes = tuple(sw_mirror_axes)
+    if sw_mirror_axes and sliding_window is None:
+        raise ValueError("evaluate: sw_mirror_axes=%r needs sliding_window (aug_eval mirrors whole volumes)" % (sw_mirror_axes,))
+    infer.tta_passes(1.0, sw_mirror_axes)            # a bad or duplicate axis raises here, before any work
 
     # the chosen prediction path as one callable -> (pred, logits, mean_probs or None)
     if aug_eval:
@@ -99,7 +106,8 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         def predict(im, ori_shape):
             return infer.sliding_window_inference(model, im, sliding_window, overlap=sw_overlap, mode=sw_mode,
                                                   sw_batch_size=sw_batch_size, ori_shape=ori_shape,
-                                                  transforms=eval_dataset.transforms.transforms) + (None,)
+                                                  transforms=eval_dataset.transforms.transforms,
+                                                  mirror_axes=sw_mirror_axes) + (None,)
     else:
         def predict(im, ori_shape):
             return infer.inference(model, im, ori_shape=ori_shape, transforms=eval_dataset.transforms.transforms) + (None,)

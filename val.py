@@ -34,7 +34,9 @@ def parse_args(argv=None):
     p.add_argument('--sw_mode', dest='sw_mode', type=str, default='gaussian', choices=('gaussian', 'constant'),
                    help='With --sliding_window: window weight')
     p.add_argument('--sw_batch_size', dest='sw_batch_size', type=int, default=1,
-                   help='With --sliding_window: windows per forward')
+                   help='With --sliding_window: windows per forward (passes per forward with --sw_mirror_axes)')
+    p.add_argument('--sw_mirror_axes', dest='sw_mirror_axes', nargs='*', type=int, default=[],
+                   help='With --sliding_window: axes to mirror every window along, 0 1 2 = D H W; every subset is one pass')
     return p.parse_args(argv)
 
 
@@ -56,7 +58,7 @@ def main(args):
                    auc_roc=args.auc_roc, save_dir=args.save_dir, hard_metrics=args.hard_metrics, auc_device=args.auc_device,
                    surface_metrics=args.surface_metrics, aug_eval=args.aug_eval, scales=args.scales,
                    flip_axes=args.flip_axes, sliding_window=args.sliding_window, sw_overlap=args.sw_overlap,
-                   sw_mode=args.sw_mode, sw_batch_size=args.sw_batch_size))
+                   sw_mode=args.sw_mode, sw_batch_size=args.sw_batch_size, sw_mirror_axes=args.sw_mirror_axes))
 
 
 if __name__ == '__main__':
