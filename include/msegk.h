@@ -713,6 +713,20 @@ int msk_resample3d(msk_ctx* ctx, const void* src, int sd, int sh, int sw, void* 
 int msk_crop_resample3d(msk_ctx* ctx, const void* src, int sd, int sh, int sw, int i, int j,
                         int k, int cd, int ch, int cw, void* dst, int dd, int dh, int dw,
                         int order, int dtype);
+/* functional.py:25-58 resize_3d / geometry.py:31-69 resample with order 3 == scipy.ndimage.zoom(order=3, mode='nearest',
+ * grid_mode=False) of the crop box (ci,cj,ck)+(sd,sh,sw) of a DEVICE float32 volume [fd,fh,fw], to dst [dd,dh,dw] float32,
+ * as tests/spline_reference.py states it, bit for bit: the box padded by 12 edge voxels per side (clamped to the BOX: the
+ * reference crops first), the recursive B-spline prefilter in float64 along D, H, W (mirror initialisation, its sum cut
+ * after 47 terms), then 4 x 4 x 4 taps around o * (n_in - 1) / (n_out - 1) + 12.  Every multiply and add is rounded on its
+ * own.  work (DEVICE, 8-byte aligned): at least msk_spline_workspace(sd, sh, sw) bytes, (sd+24)(sh+24)(sw+24) doubles;
+ * what it holds before the call does not matter and what it holds afterwards means nothing to the caller.  The query
+ * needs no context and no GPU.  Four launches on the context stream (three prefilter passes, the zoom), nothing is
+ * synchronised or downloaded.  Argument errors, reported before any launch: a null pointer, an extent < 1, a crop box
+ * outside the volume, 2^31 voxels or more (volume, padded box or destination), a workspace that is misaligned, too small
+ * or overlapping src / dst.  msk_resample3d / msk_crop_resample3d keep refusing order 3: integer volumes have none.      */
+int msk_spline_workspace(int sd, int sh, int sw, size_t* bytes);
+int msk_spline_resample3d(msk_ctx* ctx, const float* src, int fd, int fh, int fw, int ci, int cj, int ck, int sd, int sh,
+                          int sw, float* dst, int dd, int dh, int dw, void* work, size_t work_bytes);
 /* functional.py:80-88 flip_3d (np.flip along axis 0|1|2); out of place               */
 int msk_flip3d(msk_ctx* ctx, const void* src, void* dst, int d, int h, int w, int axis,
                int dtype);

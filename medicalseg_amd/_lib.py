@@ -165,6 +165,8 @@ SIGNATURES = {
     "msk_adam_clip": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _d, _d, _f, _f, _vp, _f, _f]),
     "msk_resample3d": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "msk_crop_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
+    "msk_spline_workspace": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "msk_spline_resample3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz]),
     "msk_flip3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "msk_rotate3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _i]),
     "msk_hu_norm": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f]),

@@ -106,6 +106,31 @@ def _dt(vol):
     return 0 if vol.dtype == np.float32 else 1
 
 
+def _check_order(vol, order):
+    if order not in (0, 1, 3):
+        raise ValueError("only orders 0, 1 and 3 are built, got order {}".format(order))
+    if order == 3 and vol.dtype != np.float32:
+        raise ValueError("order 3 is built for float32 volumes only (labels are resampled with order 0)")
+
+
+def _spline_device(vol: DeviceVolume, box, size, pooled) -> DeviceVolume:
+    """scipy.ndimage.zoom(order=3, mode='nearest') of the crop box (i, j, k, d, h, w) of a float32 volume
+    (msk_spline_resample3d: tests/spline_reference.py's statement bit for bit); the float64 workspace comes from the pool."""
+    dev = vol.dev
+    box = [int(v) for v in box]
+    size = tuple(int(s) for s in size)
+    nbytes = _workspace_bytes(dev, "msk_spline_workspace", *box[3:])
+    out = _new_volume(dev, size, np.float32, pooled)
+    try:
+        with _pooled_scratch(dev, nbytes) as work:
+            dev.call("msk_spline_resample3d", C.c_void_p(vol.ptr), *vol.shape, *box, C.c_void_p(out.ptr), *size,
+                     C.c_void_p(work), C.c_size_t(nbytes))
+    except BaseException:
+        out.free()
+        raise
+    return out
+
+
 def flip_device(vol: DeviceVolume, axis: int) -> DeviceVolume:
     """functional.py:80-88 flip_3d on the device."""
     out = _pooled_volume(vol.dev, vol.shape, vol.dtype)
@@ -123,6 +148,9 @@ def rotate_device(vol: DeviceVolume, r_plane, angle, order=1, cval=0) -> DeviceV
 
 def resized_crop_device(vol: DeviceVolume, i, j, k, d, h, w, size, order) -> DeviceVolume:
     """functional.py:103-110 resized_crop_3d (crop box, then zoom to `size`) on the device."""
+    _check_order(vol, order)
+    if order == 3:
+        return _spline_device(vol, (i, j, k, d, h, w), size, True)
     out = _pooled_volume(vol.dev, size, vol.dtype)
     vol.dev.call("msk_crop_resample3d", C.c_void_p(vol.ptr), *vol.shape, int(i), int(j), int(k), int(d), int(h), int(w),
                  C.c_void_p(out.ptr), *out.shape, int(order), _dt(vol))
@@ -333,8 +361,9 @@ def upload(image, dev=None) -> DeviceVolume:
 def resample_device(vol: DeviceVolume, new_shape, order=1, pooled=False) -> DeviceVolume:
     dev = vol.dev
     new_shape = tuple(int(s) for s in new_shape)
-    if order not in (0, 1):
-        raise ValueError("only order 0 and 1 are built (the orders the reference pipelines use)")
+    _check_order(vol, order)
+    if order == 3:
+        return _spline_device(vol, (0, 0, 0) + vol.shape, new_shape, pooled)
     res = _new_volume(dev, new_shape, vol.dtype, pooled)
     dev.call("msk_resample3d", C.c_void_p(vol.ptr), *vol.shape, C.c_void_p(res.ptr), *new_shape, int(order), _dt(vol))
     return res

@@ -1,3 +1,3 @@
 from .transform import (BinaryMaskToConnectComponent, Compose, RandomAffinePatchCrop3D, RandomBrightness3D, RandomContrast3D,
-                        RandomFlip3D, RandomGamma3D, RandomGaussianBlur3D, RandomGaussianNoise3D, RandomPatchCrop3D,
-                        RandomResizedCrop3D, RandomRotation3D, Resize3D, TopkLargestConnectComponent)
+                        RandomFlip3D, RandomGamma3D, RandomGaussianBlur3D, RandomGaussianNoise3D, RandomLowResolution3D,
+                        RandomPatchCrop3D, RandomResizedCrop3D, RandomRotation3D, Resize3D, TopkLargestConnectComponent)

@@ -477,6 +477,71 @@ def _blur_host(x, sigmas):
     return y
 
 
+# ---- order-3 resampling on the host: tests/spline_reference.py's statement, float64, one rounding per operator -------------
+_SPLINE_PAD = 12
+_SPLINE_HORIZON = 47
+_SPLINE_Z = np.sqrt(np.float64(3.0)) - np.float64(2.0)
+_SPLINE_GAIN = (1.0 - _SPLINE_Z) * (1.0 - 1.0 / _SPLINE_Z)
+_SPLINE_LAST = _SPLINE_Z / (_SPLINE_Z * _SPLINE_Z - 1.0)
+
+
+def _spline_taps(n_in, n_out):
+    scale = np.float64(n_in - 1) / np.float64(n_out - 1) if n_out > 1 else np.float64(0.0)
+    cc = np.arange(n_out, dtype=np.float64) * scale + np.float64(_SPLINE_PAD)
+    f = np.floor(cc)
+    t = cc - f
+    u = 1.0 - t
+    w0 = ((u * u) * u) / 6.0
+    w1 = (((t * t) * (t - 2.0)) * 3.0 + 4.0) / 6.0
+    w2 = (((u * u) * (u - 2.0)) * 3.0 + 4.0) / 6.0
+    return f.astype(np.int64) - 1, (w0, w1, w2, ((1.0 - w0) - w1) - w2)
+
+
+def _spline_zoom_host(x, out_shape):
+    """scipy.ndimage.zoom(order=3, mode='nearest') of a float32 volume as msk_spline_resample3d computes it, bit for bit:
+    12 edge voxels of padding, the recursive prefilter along each axis (the loop runs along the line, the slices span all
+    lines), then 4 x 4 x 4 taps, d outermost and w innermost."""
+    z = _SPLINE_Z
+    p = np.pad(np.asarray(x, np.float32).astype(np.float64), _SPLINE_PAD, mode="edge")
+    for axis in range(3):
+        c = np.moveaxis(p, axis, 0)
+        n = c.shape[0]
+        zn1 = np.float64(1.0)
+        for _ in range(n - 1):
+            zn1 = zn1 * z
+        c *= _SPLINE_GAIN
+        zi = z
+        c0 = c[0] + zn1 * c[n - 1]
+        for i in range(1, min(n - 2, _SPLINE_HORIZON) + 1):
+            c0 = c0 + zi * (c[i] + zn1 * c[n - 1 - i])
+            zi = zi * z
+        c[0] = c0 * (1.0 / (1.0 - zn1 * zn1))
+        for i in range(1, n):
+            c[i] = c[i] + z * c[i - 1]
+        c[n - 1] = _SPLINE_LAST * (c[n - 1] + z * c[n - 2])
+        for i in range(n - 2, -1, -1):
+            c[i] = z * (c[i + 1] - c[i])
+    out_shape = tuple(int(s) for s in out_shape)
+    (sd, wd), (sh, wh), (sw, ww) = (_spline_taps(x.shape[a], out_shape[a]) for a in range(3))
+    acc = np.zeros(out_shape, np.float64)
+    for a in range(4):
+        for b in range(4):
+            for k in range(4):
+                taps = p[(sd + a)[:, None, None], (sh + b)[None, :, None], (sw + k)[None, None, :]]
+                acc = acc + ((taps * wd[a][:, None, None]) * wh[b][None, :, None]) * ww[k][None, None, :]
+    return acc.astype(np.float32)
+
+
+def _nearest_zoom_host(x, out_shape):
+    """msk_resample3d order 0 (scipy.ndimage.zoom(order=0, mode='nearest')): the voxel at floor(o (n_in-1)/(n_out-1) + 0.5)"""
+    idx = []
+    for n_in, n_out in zip(x.shape, out_shape):
+        scale = np.float64(n_in - 1) / np.float64(n_out - 1) if n_out > 1 else np.float64(0.0)
+        i = np.floor(np.arange(int(n_out), dtype=np.float64) * scale + 0.5).astype(np.int64)
+        idx.append(np.clip(i, 0, n_in - 1))
+    return x[idx[0][:, None, None], idx[1][None, :, None], idx[2][None, None, :]]
+
+
 def _check_prob(prob):
     prob = float(prob)
     if not 0.0 <= prob <= 1.0:
@@ -653,6 +718,50 @@ class RandomGamma3D:
                 img = _gamma_host(img, gamma, self.invert, before)
                 if self.retain_stats:
                     img = _restore_host(img, before, _stats_host(img))
+        return img, label
+
+
+@manager.TRANSFORMS.add_component
+class RandomLowResolution3D:
+    """With probability ``prob``: nnU-Net's SimulateLowResolutionTransform -- the image is shrunk to
+    ``max(1, round(n * zoom))`` voxels per axis with order 0 (nearest) and brought back to its extent with order 3 (cubic
+    B-spline), zoom uniform in ``zoom`` (inside (0, 1]), one value for all axes or, with ``per_axis``, one per axis.  Both
+    steps use this project's ``scipy.ndimage.zoom(mode='nearest')`` geometry (corner-aligned coordinates); batchgenerators
+    resizes with skimage's pixel-centre map, so the voxels differ from its output although the recipe is the same.  The label
+    passes through.  Not in the reference.
+
+    Random stream, whatever the coin and the data: ``random.random()`` (coin), then one more, or three with ``per_axis``.
+    Host arrays go through ``_nearest_zoom_host`` / ``_spline_zoom_host``, device volumes through
+    ``preprocess.resample_device`` with order 0 and then 3; both are tests/spline_reference.py's statement bit for bit, so
+    one ``random.seed`` gives one result on either path."""
+
+    def __init__(self, prob=0.25, zoom=(0.5, 1.0), per_axis=False):
+        self.prob = _check_prob(prob)
+        self.zoom = _check_range(zoom, "zoom", lowest=0.0, highest=1.0)
+        if self.zoom[0] <= 0.0:
+            raise ValueError("zoom must be positive, got {}.".format(zoom))
+        self.per_axis = bool(per_axis)
+
+    def get_params(self):
+        coin = random.random()
+        u = [random.random() for _ in range(3 if self.per_axis else 1)]
+        if not self.per_axis:
+            u = u * 3
+        return coin < self.prob, [_value(self.zoom, v) for v in u]
+
+    def __call__(self, img, label=None):
+        fire, zooms = self.get_params()
+        if fire:
+            shape = tuple(int(s) for s in img.shape[:3])
+            small = tuple(max(1, int(round(n * z))) for n, z in zip(shape, zooms))
+            if _on_device(img):
+                from ..preprocess import resample_device
+                low = resample_device(img, small, 0, pooled=True)
+                out = resample_device(low, shape, 3, pooled=True)
+                low.free()
+                img = _swap(img, out)
+            else:
+                img = _spline_zoom_host(_nearest_zoom_host(np.asarray(img, np.float32), small), shape)
         return img, label
 
 
