@@ -128,6 +128,7 @@ int msk_prof_report(msk_ctx* ctx, char* buf, int buflen, int* len);
  *     "foldn_wgs" (workgroups per CU targeted by the D segmentation of conv_foldn_k, 0 = 2);
  *     "tk_join" 1|0 (msk_conv3d_bwd_bnact_join: 1 = the join backward runs in the data-gradient kernel's epilogue, 0 = it declines);
  *     "affine_map" 1|0 (msk_affine_patch: 1 = a wavefront covers a 2 x 2 x 16 box of the patch, 0 = row-linear; same results);
+ *     "topk_agg_hist" 0|1 (msk_topk_*: 1 = the first histogram pass adds a wavefront's lanes of one bin with one LDS atomic instead of one per lane; same results);
  *     "wbf_pad_min_voxels" (smallest 5^3 problem whose channel counts are not multiples of 32 that is run through the
  *         16-bit pipeline on a zero-padded copy, default 2^18);
  *     "wbf_tin_groups" (workgroups below which the pipeline's transform kernels cut their W tiles into chunks, -1 = 8 per CU, 0 = never);
@@ -641,6 +642,39 @@ int msk_region_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, 
                         int squared_pred, int batch_dice, int do_bg, int mode, float smooth, float alpha, float beta,
                         int focal_on, float gamma, const float* weight, const double* stats, float coef_f, float coef_r,
                         int accumulate, msk_tensor dlogits);
+
+/* ---- top-k selection and top-k cross entropy (TopKLoss, DiceTopKLoss: nnU-Net's TopKLoss / DC_and_topk_loss;
+ *      tests/topk_reference.py is the statement) ---- */
+/* Bytes of workspace for n values (in [1, 2^31)): the n floats of per-voxel loss, three 2048-bin histograms, 8 bytes per chunk of
+ * 4096 values.  Needs no context and no GPU.                                                                                   */
+int msk_topk_workspace(long n, size_t* bytes);
+/* record (DEVICE, 8 doubles, 8-byte aligned) = {T, K, n_gt, n_eq, S_gt, r, tie_w, S} of the K = k largest of the n float32 of x
+ * (DEVICE, 4-byte aligned, not modified).  Values are ordered by the sortable key of their bit pattern (sign bit set: all bits
+ * flipped, otherwise the sign bit set: -0.0 < +0.0, a NaN with a clear sign bit above +inf).  T = the value with the K-th
+ * largest key, n_gt / n_eq = the keys above / equal to it, S_gt = the float64 sum of the values above it in the FIXED order of
+ * msk_intensity_stats (chunks of 4096, 256 lanes, the tree, then the chunk values by the same scheme; a value that is not above T
+ * adds +0.0), r = K - n_gt, tie_w = r / n_eq, S = S_gt + r T (a product, then a sum).  k == 0: all zeros.  Every field is exact.
+ * One memset and five launches on the context stream: three histogram passes over digits of 11, 11 and 10 bits (integer LDS
+ * and global atomics), the ordered sum, the finish.  No float atomics, no synchronisation, no download.  workspace (DEVICE): 16-byte aligned,
+ * msk_topk_workspace(n) bytes, overlapping neither x nor record; its contents mean nothing to the caller.                       */
+int msk_topk_select(msk_ctx* ctx, const float* x, long n, long k, void* workspace, double* record);
+/* Top-k cross entropy of logits [N,D,H,W,C] (ld >= C, 2 <= C <= 64, V = N D H W < 2^31) against int32 labels.  A voxel is valid
+ * when its label is in [0, C) and is not ignore_index.  l_i = w_y (logf(sum_c expf(z_c - m)) - (z_y - m)), m the row maximum,
+ * w = weights (DEVICE, [C], all >= 0) or ones when NULL; an invalid voxel gets the sentinel -1.  K = floor((double)n_valid *
+ * (double)k_percent / 100), at least 1 when n_valid > 0, evaluated on the device; record = the msk_topk_select record of the l_i
+ * for that K; out (DEVICE, 2 + C floats) = {S / K (0 when n_valid == 0), 0, ...}.  The l_i stay in the workspace (its first V
+ * floats) for the backward call.  One memset and five launches; nothing is downloaded and nothing synchronises.  With several
+ * ranks the selection is that of the calling rank.                                                                              */
+int msk_topk_ce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const float* weights,
+                    float k_percent, void* workspace, float* out, double* record);
+/* dz (+)= coef u_i w_y (softmax(z_i) - onehot(y_i)) / K from the workspace and the record of the forward call: u_i = 1 for
+ * l_i above T, tie_w for l_i at T (tied voxels share the remaining weight: a subgradient with the loss's value that needs no
+ * raster order), 0 below and at invalid voxels (exact zeros).  Membership compares the stored l_i, so it is the forward's bit
+ * for bit.  accumulate != 0 adds into dz.  One launch.  Argument errors of all four, reported before any launch: null or
+ * misaligned pointers, n or V outside [1, 2^31), k outside [0, n], k_percent outside (0, 100], C outside 2..64, a dz of another
+ * shape, a workspace that overlaps an operand.                                                                                  */
+int msk_topk_ce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const float* weights,
+                    const void* workspace, const double* record, float coef, int accumulate, msk_tensor dz);
 
 /* ---- optimizer --------------------------------------------------------------- */
 /* paddle.optimizer.Momentum(momentum, weight_decay=L2) over one flat arena

@@ -155,6 +155,10 @@ SIGNATURES = {
     "msk_bce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _i, _T]),
     "msk_region_loss_fwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _vp]),
     "msk_region_loss_bwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _i, _T]),
+    "msk_topk_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
+    "msk_topk_select": (_i, [_vp, _vp, C.c_long, C.c_long, _vp, _vp]),
+    "msk_topk_ce_fwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _vp, _vp, _vp]),
+    "msk_topk_ce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _vp, _vp, _f, _i, _T]),
     "msk_sgd_momentum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_eager": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_finish": (_i, [_vp]),

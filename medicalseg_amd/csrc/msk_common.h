@@ -156,6 +156,7 @@ struct msk_ctx {
   std::vector<int> host_fds;
   int rank = 0, world = 1;
   int tk_join = 1;   // option "tk_join": msk_conv3d_bwd_bnact_join may run the join backward in the epilogue of conv_tk_h2_k; 0 = it declines (A/B, tests)
+  int topk_agg_hist = 0;   // option "topk_agg_hist": the first-digit LDS histogram of msk_loss_topk.hip goes through msk_count_slot (one atomic per bin and wavefront) instead of one atomic per lane, which measured faster (A/B, tools/bench_topk.py; same results)
   int affine_map = 1;   // option "affine_map": thread -> voxel map of msk_affine_patch: 1 = a 2 x 2 x 16 box per wavefront, 0 = row-linear (A/B, tools/bench_affine.py)
   int num_cu = 256;
 };

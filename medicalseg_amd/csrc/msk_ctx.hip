@@ -632,6 +632,10 @@ int msk_set_option(msk_ctx* ctx, const char* key, int value) {
     ctx->affine_map = value != 0;
     return 0;
   }
+  if (strcmp(key, "topk_agg_hist") == 0) {  // msk_topk_*: 1 = same-bin aggregation (msk_count_slot) in the first histogram pass (A/B)
+    ctx->topk_agg_hist = value != 0;
+    return 0;
+  }
   if (strcmp(key, "foldn_wgs") == 0) {
     ctx->foldn_wgs = value > 0 ? value : 0;
     return 0;

@@ -4,3 +4,4 @@ from .dice_loss import DiceLoss
 from .mixes_losses import MixedLoss
 from .binary_cross_entropy_loss import BCELoss
 from .region_losses import DiceCELoss, FocalLoss, SoftDiceLoss, TverskyLoss
+from .topk_losses import DiceTopKLoss, TopKLoss

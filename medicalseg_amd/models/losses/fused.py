@@ -204,6 +204,40 @@ class RegionNode(Node):
                       accumulate, dz.msk())
 
 
+class TopKNode(Node):
+    """Top-k cross entropy (the 'topk' term, out[0]): msk_topk_ce_fwd / msk_topk_ce_bwd.  `settings` is (ignore_index, k,
+    weight_ptr): k the percentage of the valid voxels that count, weight_ptr the device vector of per-class weights or None.
+    The workspace (the per-voxel losses the backward pass compares against the threshold) and the record come from the
+    activation arena: they live until the next model forward, like the other records.  K, the threshold and the tie weight
+    stay on the device.  With several ranks the selection is that of this rank's batch."""
+    SLOTS = {"topk": 0}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.ignore_index, self.k, self.weight_ptr = settings
+        self.ws_ptr = None
+
+    def stats_doubles(self):
+        return 8
+
+    def _args(self):
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(self.ignore_index), C.c_void_p(self.weight_ptr))
+
+    def _forward(self):
+        if self.ws_ptr is None:
+            nbytes = C.c_size_t(0)
+            voxels = self.logits.n * self.logits.d * self.logits.h * self.logits.w
+            if self.dev.lib.msk_topk_workspace(C.c_long(voxels), C.byref(nbytes)) != 0:
+                raise ValueError("msk_topk_workspace refused %d voxels" % voxels)
+            self.ws_ptr = self.dev.arena.alloc(nbytes.value)
+        self.dev.call("msk_topk_ce_fwd", *self._args(), C.c_float(self.k), C.c_void_p(self.ws_ptr), C.c_void_p(self.out_ptr),
+                      C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef, _, accumulate, dz):
+        self.dev.call("msk_topk_ce_bwd", *self._args(), C.c_void_p(self.ws_ptr), C.c_void_p(self.stats_ptr), C.c_float(coef),
+                      accumulate, dz.msk())
+
+
 _CACHE = {}     # kind -> {key: node}
 
 
@@ -224,7 +258,7 @@ def node_for(kind, logits: Tensor, labels, settings=()):
 
 
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce'): the float node.slot(which) of the node's
+    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce' | 'topk'): the float node.slot(which) of the node's
     record.  Values stay on the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 
