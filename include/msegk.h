@@ -676,6 +676,55 @@ int msk_topk_ce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int 
 int msk_topk_ce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const float* weights,
                     const void* workspace, const double* record, float coef, int accumulate, msk_tensor dz);
 
+/* ---- foreground statistics, percentile clipping, z-scoring and the non-zero bounding box (nnU-Net's crop_to_nonzero,
+ *      CTNormalization, ZScoreNormalization; preprocess.fg_stats_device / clip_zscore_device / nonzero_bbox_device;
+ *      tests/normalize_reference.py is the statement) ---- */
+#define MSK_MASK_ALL 0      /* every voxel is valid */
+#define MSK_MASK_NONZERO 1  /* x != 0 (so -0.0 is outside): nnU-Net's non-zero mask without its hole filling */
+#define MSK_MASK_LABEL 2    /* mask > 0, mask an int32 buffer of n words */
+#define MSK_NORM_CLIP 1     /* flags of msk_clip_zscore */
+#define MSK_NORM_ZSCORE 2
+#define MSK_NORM_MASK_OUT 4
+/* Bytes of workspace msk_fg_stats needs for n values (in [1, 2^31)): five 2048-bin histograms and 32 bytes per chunk of 4096
+ * values.  Needs no context and no GPU.                                                                                       */
+int msk_fg_stats_workspace(long n, size_t* bytes);
+/* record (DEVICE, 16 doubles, 8-byte aligned) = {n_valid, min, max, sum, sumsq, mean, std, p_lo, p_hi, a_lo, b_lo, g_lo, a_hi,
+ * b_hi, g_hi, 0} of the valid voxels among the n float32 of x (DEVICE, 4-byte aligned, finite, not modified); mask (DEVICE, n
+ * int32, not modified) is read with MSK_MASK_LABEL only and may be NULL otherwise.  Values are ordered by msk_topk_select's
+ * sortable key; s = the valid values in ascending order.  n_valid, min = s[0], max = s[n_valid-1] are exact; sum and sumsq are
+ * float64 sums in the FIXED order of msk_intensity_stats over the full raster, an invalid voxel adding +0.0; mean = sum /
+ * n_valid, std = sqrt(max(sumsq / n_valid - mean * mean, 0)).  Percentiles (numpy's default method): h = (n_valid - 1) *
+ * (q / 100.0), i = floor(h), g = h - i, a = s[i], b = s[min(i + 1, n_valid - 1)], d = b - a, p = g >= 0.5 ? b - d * (1 - g) :
+ * a + d * g; K = n_valid - i, h, i and g are evaluated on the device.  Every operation is a float64 operation rounded on its
+ * own; every field is exact.  n_valid == 0: all zeros.  One memset and five launches on the context stream: three histogram
+ * passes that carry both order statistics (integer LDS and global atomics), the ordered sums with the minimum above each a
+ * riding along, the finish.  No float atomics, no synchronisation, no download.  workspace (DEVICE): 16-byte aligned,
+ * msk_fg_stats_workspace(n) bytes, overlapping neither x, mask nor record; its contents mean nothing to the caller.
+ * Non-finite x gives unspecified values but no access outside the buffers.                                                    */
+int msk_fg_stats(msk_ctx* ctx, const float* x, const int32_t* mask, long n, int mask_mode, double q_lo, double q_hi,
+                 void* workspace, double* record);
+/* One streaming pass over n float32 (DEVICE, 4-byte aligned; 16 bytes per lane where x, y and a mask that is read are 16-byte
+ * aligned; y == x is allowed, any other overlap is an error).  lo = (float)p_lo, hi = (float)p_hi, m = (float)mean, inv =
+ * (float)(1.0 / max(std, 1e-8)) come from record (DEVICE, a msk_fg_stats record, read on the device behind the thread's first
+ * loads: nothing synchronises) or, when record is NULL, from host_params (HOST, 4 doubles {lo, hi, mean, std}, read before the
+ * call returns); the two give the same bits for the same values.  In float32, every operation rounded on its own:
+ * c = x < lo ? lo : x;  c = c > hi ? hi : c (MSK_NORM_CLIP);  y = (c - m) * inv (MSK_NORM_ZSCORE).  With MSK_NORM_MASK_OUT a voxel
+ * that is not valid under mask_mode (see msk_fg_stats; mask is read with MSK_MASK_LABEL and MSK_NORM_MASK_OUT only) becomes
+ * `outside`; otherwise it is transformed like every other voxel.  One launch.                                                 */
+int msk_clip_zscore(msk_ctx* ctx, const float* x, const int32_t* mask, long n, int mask_mode, const double* record,
+                    const double* host_params, int flags, float outside, float* y);
+/* box (DEVICE, 8 int32, 4-byte aligned) = {d0, h0, w0, d1, h1, w1, count, 0} of the non-zero voxels of a [d, h, w] volume
+ * (DEVICE, 4-byte aligned, not modified; dtype 0 = float32: x != 0, a NaN counts; 1 = int32: v != 0): the upper corner is
+ * exclusive, all zeros for an empty volume.  Filling holes does not change a bounding box, so this is the box of nnU-Net's filled
+ * mask.  One memset, one streaming pass and a one-thread finish on the context stream; a workgroup reduces its six extremes and
+ * its count in registers and LDS and, only if it saw a non-zero voxel, adds its count and sends the extremes that still move the
+ * record (at most seven integer atomics).  Nothing synchronises.
+ * Argument errors of all four, reported before any launch: null pointers, n outside [1, 2^31), extents < 1 or 2^31 voxels and
+ * more, q outside [0, 100] or q_lo > q_hi, an unknown mask_mode / dtype / flag, MSK_MASK_LABEL without a mask, a misaligned
+ * record or box, a workspace that is misaligned or overlaps an operand (its size is not passed: the caller owes
+ * msk_fg_stats_workspace(n) bytes).                                                                                           */
+int msk_nonzero_bbox(msk_ctx* ctx, const void* src, int d, int h, int w, int dtype, int32_t* box);
+
 /* ---- optimizer --------------------------------------------------------------- */
 /* paddle.optimizer.Momentum(momentum, weight_decay=L2) over one flat arena
  * (cvlibs/config.py:212-214): g += wd*p; v = mu*v + g; p -= lr*v.

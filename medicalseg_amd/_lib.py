@@ -159,6 +159,10 @@ SIGNATURES = {
     "msk_topk_select": (_i, [_vp, _vp, C.c_long, C.c_long, _vp, _vp]),
     "msk_topk_ce_fwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     "msk_topk_ce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _vp, _vp, _f, _i, _T]),
+    "msk_fg_stats_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
+    "msk_fg_stats": (_i, [_vp, _vp, _vp, C.c_long, _i, _d, _d, _vp, _vp]),
+    "msk_clip_zscore": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp, _i, _f, _vp]),
+    "msk_nonzero_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "msk_sgd_momentum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_eager": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_finish": (_i, [_vp]),

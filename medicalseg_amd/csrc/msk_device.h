@@ -439,3 +439,100 @@ __device__ __forceinline__ msk_red_vals msk_red_finish(long nc, const double* __
   r.mx = STATS ? tmx[0] : 0.f;
   return r;
 }
+
+// ---- the radix select's keys, histograms and digit resolution ----------------------------------------------------------------------
+// What msk_loss_topk.hip (the K-th largest loss) and msk_normalize.hip (two order statistics of the valid voxels) share; the
+// statements are tests/topk_reference.py and tests/normalize_reference.py.  Values are ordered by the sortable key of their bit
+// pattern (sign set: all bits flipped, else the sign bit set: -0.0 < +0.0, nothing is left to a float comparison).  Three digits
+// of 11, 11 and 10 bits, most significant first; a workgroup of 256 threads counts a digit in an LDS histogram of 2048 bins and
+// merges it into a global one with integer atomics, and every later pass rescans the global histograms in its prologue.
+constexpr int kMskSelThreads = 256;
+constexpr int kMskSelPasses = 3;     // digits of 11, 11 and 10 bits, most significant first
+constexpr int kMskSelBins = 2048;    // bins per digit: eight consecutive bins per thread of the workgroup that rescans a histogram
+constexpr int kMskSelBinsPerThread = kMskSelBins / kMskSelThreads;
+__host__ __device__ constexpr int msk_sel_shift(int p) { return p == 0 ? 21 : (p == 1 ? 10 : 0); }
+__host__ __device__ constexpr int msk_sel_width(int p) { return p == 2 ? 10 : 11; }
+
+__device__ __forceinline__ uint32_t msk_sel_key(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float msk_sel_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+struct msk_sel {
+  uint32_t K;        // 0: nothing is selected, the other fields mean nothing
+  uint32_t prefix;   // the digits of the K-th largest key found so far
+  uint32_t krem;     // the rank sought among the keys that carry them
+  uint32_t ngt;      // keys above every key that carries them
+  uint32_t neq;      // keys that carry them
+};
+
+// a thread's eight consecutive bins of the global histograms of passes 0 .. NP-1 (16-byte aligned): asked for at once, one round trip
+template <int NP>
+struct msk_sel_bins {
+  uint4 lo[NP], hi[NP];
+};
+template <int NP>
+__device__ __forceinline__ msk_sel_bins<NP> msk_sel_load(const uint32_t* const* hist) {
+  msk_sel_bins<NP> b;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const uint4* h = reinterpret_cast<const uint4*>(hist[p]) + 2 * threadIdx.x;
+    b.lo[p] = h[0];
+    b.hi[p] = h[1];
+  }
+  return b;
+}
+
+// The first NP digits of the K-th largest key from the bins msk_sel_load returned; K <= the number of keys.  Called by all 256
+// threads; s_scan: 8 LDS words.  Per digit a thread holds eight consecutive bins: the exclusive scan over the threads ABOVE
+// it, then the one thread with above < krem <= above + count walks its bins down from the top.  K == 0 returns before any
+// barrier (K must be uniform over the workgroup).
+template <int NP>
+__device__ __forceinline__ msk_sel msk_sel_scan(const msk_sel_bins<NP>& b, uint32_t K, uint32_t* s_scan) {
+  msk_sel s = {K, 0u, K, 0u, 0u};
+  if (K == 0) return s;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const uint32_t c8[kMskSelBinsPerThread] = {b.lo[p].x, b.lo[p].y, b.lo[p].z, b.lo[p].w, b.hi[p].x, b.hi[p].y, b.hi[p].z, b.hi[p].w};
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kMskSelBinsPerThread; ++j) c += c8[j];
+    uint32_t above = msk_block_excl_scan<true>(c, 0u, msk_op_add(), s_scan);
+    if (s.krem > above && s.krem - above <= c) {
+      int j = kMskSelBinsPerThread - 1;
+      for (; j > 0 && s.krem - above > c8[j]; --j) above += c8[j];
+      s_scan[4] = kMskSelBinsPerThread * threadIdx.x + j;
+      s_scan[5] = above;
+      s_scan[6] = c8[j];
+    }
+    __syncthreads();   // (the next digit writes these words behind the two barriers of its scan)
+    s.prefix = (s.prefix << msk_sel_width(p)) | s_scan[4];
+    s.ngt += s_scan[5];
+    s.krem -= s_scan[5];
+    s.neq = s_scan[6];
+  }
+  return s;
+}
+
+// the workgroup's LDS histogram: cleared (a barrier must follow) and added to the global one (behind a barrier); empty bins cost
+// no atomic (adding them too, so that a wavefront's atomics cover consecutive words, was measured 4 us per pass slower)
+__device__ __forceinline__ void msk_sel_hist_clear(uint32_t* __restrict__ s_hist) {
+  for (int b = threadIdx.x; b < kMskSelBins; b += kMskSelThreads) s_hist[b] = 0u;
+}
+__device__ __forceinline__ void msk_sel_hist_merge(const uint32_t* __restrict__ s_hist, uint32_t* __restrict__ g_hist) {
+  for (int b = threadIdx.x; b < kMskSelBins; b += kMskSelThreads) {
+    const uint32_t c = s_hist[b];
+    if (c) atomicAdd(&g_hist[b], c);
+  }
+}
+
+// the tree of msk_red_chunk over the four lane values a thread of the chunk's wavefront carries
+__device__ __forceinline__ double msk_red_chunk_tree(double (&s)[4]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {                     // s = 128 .. 4 of the tree
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = s[i] + msk_shfl_xor_d(s[i], o);
+  }
+  return (s[0] + s[2]) + (s[1] + s[3]);                  // s = 2, then s = 1
+}

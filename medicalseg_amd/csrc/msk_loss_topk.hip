@@ -34,11 +34,9 @@ namespace {
 
 constexpr int kThreads = 256;
 static_assert(kThreads == kTpvThreads, "the tpv_* helpers of msk_device.h assume this workgroup");
-constexpr int kPasses = 3;     // digits of 11, 11 and 10 bits, most significant first
-constexpr int kBins = 2048;    // bins per digit: eight consecutive bins per thread of the workgroup that rescans a histogram
-constexpr int kBinsPerThread = kBins / kThreads;
-__host__ __device__ constexpr int topk_shift(int p) { return p == 0 ? 21 : (p == 1 ? 10 : 0); }
-__host__ __device__ constexpr int topk_width(int p) { return p == 2 ? 10 : 11; }
+constexpr int kPasses = kMskSelPasses;
+constexpr int kBins = kMskSelBins;
+static_assert(kThreads == kMskSelThreads, "the msk_sel_* helpers of msk_device.h assume this workgroup");
 
 struct TopkCtl {               // zeroed by one memset per call
   uint32_t hist[kPasses][kBins];
@@ -65,34 +63,16 @@ inline TopkWs topk_ws(void* w, long n) {
   return s;
 }
 
-__device__ __forceinline__ uint32_t topk_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float topk_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-struct TopkSel {
-  uint32_t K;        // 0: nothing is selected, the other fields mean nothing
-  uint32_t prefix;   // the digits of key(T) found so far
-  uint32_t krem;     // the rank sought among the keys that carry them
-  uint32_t ngt;      // keys above every key that carries them
-  uint32_t neq;      // keys that carry them
-};
-
 // K -- the caller's (k_arg >= 0) or floor(n_valid * k_percent / 100), at least 1 when there is a valid voxel -- and the first NP
-// digits of the K-th largest key from the global histograms of passes 0 .. NP-1; K <= the number of keys.  Called by all 256
-// threads; s_scan: 8 LDS words.  Everything is asked for at once (one round trip).  Per digit a thread holds eight consecutive
-// bins: the exclusive scan over the threads ABOVE it, then the one thread with above < krem <= above + count walks its bins down
-// from the top.  K == 0 returns before any barrier (uniform).
+// digits of the K-th largest key from the global histograms of passes 0 .. NP-1 (msk_sel_load / msk_sel_scan of msk_device.h);
+// K <= the number of keys.  Called by all 256 threads; s_scan: 8 LDS words.  Everything is asked for at once (one round trip).
+// K == 0 returns before any barrier (uniform).
 template <int NP>
-__device__ __forceinline__ TopkSel topk_resolve(const TopkCtl* __restrict__ ctl, long k_arg, float kpct, uint32_t* s_scan) {
-  uint4 lo[NP], hi[NP];
+__device__ __forceinline__ msk_sel topk_resolve(const TopkCtl* __restrict__ ctl, long k_arg, float kpct, uint32_t* s_scan) {
+  const uint32_t* hist[NP];
 #pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const uint4* h = reinterpret_cast<const uint4*>(ctl->hist[p]) + 2 * threadIdx.x;
-    lo[p] = h[0];
-    hi[p] = h[1];
-  }
+  for (int p = 0; p < NP; ++p) hist[p] = ctl->hist[p];
+  const msk_sel_bins<NP> bins = msk_sel_load<NP>(hist);
   const uint32_t nv = ctl->n_valid;
   uint32_t K;
   if (k_arg >= 0) {
@@ -101,29 +81,7 @@ __device__ __forceinline__ TopkSel topk_resolve(const TopkCtl* __restrict__ ctl,
     K = (uint32_t)floor((double)nv * (double)kpct / 100.0);
     if (nv > 0 && K < 1) K = 1;
   }
-  TopkSel s = {K, 0u, K, 0u, 0u};
-  if (K == 0) return s;
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const uint32_t c8[kBinsPerThread] = {lo[p].x, lo[p].y, lo[p].z, lo[p].w, hi[p].x, hi[p].y, hi[p].z, hi[p].w};
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kBinsPerThread; ++j) c += c8[j];
-    uint32_t above = msk_block_excl_scan<true>(c, 0u, msk_op_add(), s_scan);
-    if (s.krem > above && s.krem - above <= c) {
-      int j = kBinsPerThread - 1;
-      for (; j > 0 && s.krem - above > c8[j]; --j) above += c8[j];
-      s_scan[4] = kBinsPerThread * threadIdx.x + j;
-      s_scan[5] = above;
-      s_scan[6] = c8[j];
-    }
-    __syncthreads();   // (the next digit writes these words behind the two barriers of its scan)
-    s.prefix = (s.prefix << topk_width(p)) | s_scan[4];
-    s.ngt += s_scan[5];
-    s.krem -= s_scan[5];
-    s.neq = s_scan[6];
-  }
-  return s;
+  return msk_sel_scan<NP>(bins, K, s_scan);
 }
 
 // one value per lane into the workgroup's LDS histogram, digit < 0 = nothing; called by every lane of the wavefront
@@ -134,18 +92,6 @@ __device__ __forceinline__ void topk_count(int digit, uint32_t* __restrict__ s_h
     atomicAdd(&s_hist[digit], 1u);
   }
 }
-// the workgroup's LDS histogram: cleared (a barrier must follow) and added to the global one (behind a barrier); empty bins cost
-// no atomic (adding them too, so that a wavefront's atomics cover consecutive words, was measured 4 us per pass slower)
-__device__ __forceinline__ void topk_hist_clear(uint32_t* __restrict__ s_hist) {
-  for (int b = threadIdx.x; b < kBins; b += kThreads) s_hist[b] = 0u;
-}
-__device__ __forceinline__ void topk_hist_merge(const uint32_t* __restrict__ s_hist, uint32_t* __restrict__ g_hist) {
-  for (int b = threadIdx.x; b < kBins; b += kThreads) {
-    const uint32_t c = s_hist[b];
-    if (c) atomicAdd(&g_hist[b], c);
-  }
-}
-
 // digit P of the keys whose digits 0 .. P-1 are those of the K-th largest key; grid-stride over quads (vec: x is 16-byte aligned)
 // or single elements.  Every trip count is uniform over the workgroup: topk_count is reached by whole wavefronts.
 template <int P>
@@ -153,7 +99,7 @@ __global__ void __launch_bounds__(kThreads)
 topk_hist_k(const float* __restrict__ x, long n, int vec, TopkCtl* __restrict__ ctl, long k_arg, float kpct, int agg_on) {
   __shared__ uint32_t s_hist[kBins];
   __shared__ uint32_t s_scan[8];
-  topk_hist_clear(s_hist);
+  msk_sel_hist_clear(s_hist);
   const long stride = (long)gridDim.x * kThreads;
   const long n4 = n >> 2;
   const float4* x4 = reinterpret_cast<const float4*>(x);
@@ -163,7 +109,7 @@ topk_hist_k(const float* __restrict__ x, long n, int vec, TopkCtl* __restrict__ 
   if (vec && i < n4) cur = x4[i];
   uint32_t prefix = 0u;
   if (P > 0) {
-    const TopkSel sel = topk_resolve<(P > 0 ? P : 1)>(ctl, k_arg, kpct, s_scan);
+    const msk_sel sel = topk_resolve<(P > 0 ? P : 1)>(ctl, k_arg, kpct, s_scan);
     if (sel.K == 0) return;                              // uniform: the record is all zeros
     prefix = sel.prefix;
   } else {
@@ -172,11 +118,11 @@ topk_hist_k(const float* __restrict__ x, long n, int vec, TopkCtl* __restrict__ 
   // same-bin aggregation (msk_count_slot) only where it is asked for and only for the first digit: behind it the digits
   // scatter and few lanes still carry the prefix
   const bool agg = P == 0 && agg_on;
-  constexpr int kDigitShift = topk_shift(P);
-  constexpr uint32_t kDigitMask = (1u << topk_width(P)) - 1u;
+  constexpr int kDigitShift = msk_sel_shift(P);
+  constexpr uint32_t kDigitMask = (1u << msk_sel_width(P)) - 1u;
   auto digit_of = [&](float f) -> int {
-    const uint32_t key = topk_key(f);
-    if (P > 0 && (key >> (kDigitShift + topk_width(P))) != prefix) return -1;
+    const uint32_t key = msk_sel_key(f);
+    if (P > 0 && (key >> (kDigitShift + msk_sel_width(P))) != prefix) return -1;
     return (int)((key >> kDigitShift) & kDigitMask);
   };
   const int lane = threadIdx.x & 63;
@@ -204,7 +150,7 @@ topk_hist_k(const float* __restrict__ x, long n, int vec, TopkCtl* __restrict__ 
     }
   }
   __syncthreads();
-  topk_hist_merge(s_hist, ctl->hist[P]);
+  msk_sel_hist_merge(s_hist, ctl->hist[P]);
 }
 
 // l = w_y (log sum_c exp(z_c - max) - (z_y - max)): the arithmetic of region_probs / region_stats_k at gamma = 0
@@ -231,7 +177,7 @@ topk_ce_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ label
   __shared__ float s_w[64];
   __shared__ uint32_t s_hist[kBins];
   __shared__ uint32_t s_nvalid;
-  topk_hist_clear(s_hist);
+  msk_sel_hist_clear(s_hist);
   if (threadIdx.x == 0) s_nvalid = 0u;
   if (threadIdx.x < 64) s_w[threadIdx.x] = (weight != nullptr && (int)threadIdx.x < C) ? weight[threadIdx.x] : 1.f;
   __syncthreads();
@@ -255,12 +201,12 @@ topk_ce_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ label
       ++nvalid;
     }
     if (mine) loss[v] = l;
-    topk_count(mine ? (int)(topk_key(l) >> topk_shift(0)) : -1, s_hist, lane, agg_on != 0);
+    topk_count(mine ? (int)(msk_sel_key(l) >> msk_sel_shift(0)) : -1, s_hist, lane, agg_on != 0);
   }
   nvalid = msk_wave_sum_u32(nvalid);
   if (lane == 0 && nvalid) atomicAdd(&s_nvalid, nvalid);
   __syncthreads();
-  topk_hist_merge(s_hist, ctl->hist[0]);
+  msk_sel_hist_merge(s_hist, ctl->hist[0]);
   if (threadIdx.x == 0 && s_nvalid) atomicAdd(&ctl->n_valid, s_nvalid);   // one single-word atomic per workgroup, not per wavefront
 }
 
@@ -272,23 +218,15 @@ __device__ __forceinline__ void topk_chunk_load(const float* __restrict__ chunk0
 #pragma unroll
   for (int j = 0; j < 16; ++j) v[j] = x4[64 * j + m];
 }
-__device__ __forceinline__ double topk_chunk_tree(double (&s)[4]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                     // s = 128 .. 4 of the tree
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] = s[i] + msk_shfl_xor_d(s[i], o);
-  }
-  return (s[0] + s[2]) + (s[1] + s[3]);                  // s = 2, then s = 1
-}
 __device__ __forceinline__ double topk_chunk_sum_loaded(const float4 (&v)[16], uint32_t tkey) {
   double s[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const float e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] = s[i] + (topk_key(e[i]) > tkey ? (double)e[i] : 0.0);
+    for (int i = 0; i < 4; ++i) s[i] = s[i] + (msk_sel_key(e[i]) > tkey ? (double)e[i] : 0.0);
   }
-  return topk_chunk_tree(s);
+  return msk_red_chunk_tree(s);
 }
 __device__ __forceinline__ double topk_chunk_sum_ragged(const float* __restrict__ xc, long left, int m, uint32_t tkey) {
   double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -299,12 +237,12 @@ __device__ __forceinline__ double topk_chunk_sum_ragged(const float* __restrict_
       double d = 0.0;
       if (e < left) {
         const float f = xc[e];
-        if (topk_key(f) > tkey) d = (double)f;
+        if (msk_sel_key(f) > tkey) d = (double)f;
       }
       s[i] = s[i] + d;
     }
   }
-  return topk_chunk_tree(s);
+  return msk_red_chunk_tree(s);
 }
 
 constexpr int kSumChunks = kThreads / 64;                // chunks per workgroup of topk_sum_k
@@ -320,7 +258,7 @@ topk_sum_k(const float* __restrict__ x, long n, int vec, long nc, const TopkCtl*
   const bool whole = active && vec && n - base >= kMskRedChunk;
   float4 v[16];
   if (whole) topk_chunk_load(x + base, m, v);            // in flight while the histograms are read and scanned
-  const TopkSel sel = topk_resolve<kPasses>(ctl, k_arg, kpct, s_scan);
+  const msk_sel sel = topk_resolve<kPasses>(ctl, k_arg, kpct, s_scan);
   if (sel.K == 0) return;                                // uniform; the finish pass does not read the chunk values then
   const uint32_t tkey = sel.prefix;
   if (!active) return;                                   // behind the last barrier
@@ -333,7 +271,7 @@ __global__ void __launch_bounds__(kMskRedLanes)
 topk_finish_k(long nc, const TopkCtl* __restrict__ ctl, long k_arg, float kpct, const double* __restrict__ partial,
               double* __restrict__ rec, float* __restrict__ out, int C) {
   __shared__ uint32_t s_scan[8];
-  const TopkSel sel = topk_resolve<kPasses>(ctl, k_arg, kpct, s_scan);
+  const msk_sel sel = topk_resolve<kPasses>(ctl, k_arg, kpct, s_scan);
   const uint32_t K = sel.K;
   if (out != nullptr && (int)threadIdx.x >= 1 && (int)threadIdx.x < 2 + C) out[threadIdx.x] = 0.f;
   if (K == 0) {
@@ -343,7 +281,7 @@ topk_finish_k(long nc, const TopkCtl* __restrict__ ctl, long k_arg, float kpct, 
   }
   const msk_red_vals red = msk_red_finish<false>(nc, nullptr, partial, nullptr, nullptr);
   if (threadIdx.x == 0) {
-    const double T = (double)topk_unkey(sel.prefix);
+    const double T = (double)msk_sel_unkey(sel.prefix);
     const double r = (double)(K - sel.ngt);              // >= 1: fewer than K keys are above the K-th largest
     const double S = __dadd_rn(red.sumsq, __dmul_rn(r, T));   // two roundings, as the statement has them
     rec[0] = T;
@@ -377,7 +315,7 @@ topk_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labe
   }
   if (threadIdx.x < 64) s_w[threadIdx.x] = (weight != nullptr && (int)threadIdx.x < C) ? weight[threadIdx.x] : 1.f;
   const double Kd = rec[1];
-  const uint32_t tkey = topk_key((float)rec[0]);
+  const uint32_t tkey = msk_sel_key((float)rec[0]);
   const float tie = (float)rec[6];
   const float scale = Kd > 0.0 ? (float)((double)coef / Kd) : 0.f;
   __syncthreads();
@@ -390,7 +328,7 @@ topk_bwd_k(const float* __restrict__ z, int ld, const int32_t* __restrict__ labe
     const bool valid = mine && y != ignore_index && (unsigned)y < (unsigned)C;
     float u = 0.f;
     if (valid && Kd > 0.0) {
-      const uint32_t key = topk_key(lv);
+      const uint32_t key = msk_sel_key(lv);
       u = key > tkey ? 1.f : (key == tkey ? tie : 0.f);
     }
     const int yv = y;

@@ -337,6 +337,307 @@ def gauss_blur_device(vol: DeviceVolume, sigma) -> DeviceVolume:
     return out
 
 
+# ---- non-zero cropping, percentile clipping and z-scoring (nnU-Net's crop_to_nonzero, CTNormalization, ZScoreNormalization;
+#      MONAI's ScaleIntensityRangePercentiles / NormalizeIntensity(nonzero=True)) --------------------------------------------------
+MASK_MODES = {"all": 0, "nonzero": 1, "mask": 2}       # MSK_MASK_*
+NORM_CLIP, NORM_ZSCORE, NORM_MASK_OUT = 1, 2, 4        # MSK_NORM_*
+FG_FIELDS = ("n_valid", "min", "max", "sum", "sumsq", "mean", "std", "p_lo", "p_hi", "a_lo", "b_lo", "g_lo", "a_hi", "b_hi", "g_hi")
+
+
+def _mask_mode(mode, mask):
+    if mode not in MASK_MODES:
+        raise ValueError("mode must be one of 'all', 'nonzero', 'mask', got {!r}".format(mode))
+    if (mode == "mask") != (mask is not None):
+        raise ValueError("mode 'mask' takes a mask and the other modes take none")
+    return MASK_MODES[mode]
+
+
+def _percentile_pair(percentiles):
+    q = [float(v) for v in percentiles]
+    if len(q) != 2 or not 0.0 <= q[0] <= q[1] <= 100.0:
+        raise ValueError("percentiles must be two values 0 <= lo <= hi <= 100, got {}".format(percentiles))
+    return q
+
+
+def _norm_params(stats, lo, hi, mean, std, clip, zscore):
+    """the four doubles {lo, hi, mean, std} of the apply pass from explicit values (None when a record supplies them)"""
+    if not (clip or zscore):
+        raise ValueError("at least one of clip and zscore must be on")
+    given = [v is not None for v in (lo, hi, mean, std)]
+    if stats is not None:
+        if any(given):
+            raise ValueError("give a statistics record or explicit values, not both")
+        return None
+    if clip and not (given[0] and given[1]):
+        raise ValueError("clip needs lo and hi (or a statistics record)")
+    if zscore and not (given[2] and given[3]):
+        raise ValueError("zscore needs mean and std (or a statistics record)")
+    p = np.array([lo if clip else 0.0, hi if clip else 0.0, mean if zscore else 0.0, std if zscore else 1.0], np.float64)
+    if clip and not p[0] <= p[1]:
+        raise ValueError("lo must not exceed hi, got {} > {}".format(lo, hi))
+    return p
+
+
+def _mask_volume(vol, mask, what):
+    if not isinstance(mask, DeviceVolume) or mask.dtype != np.int32 or mask.size != vol.size:
+        raise TypeError("{} takes an int32 DeviceVolume of the volume's size as the mask".format(what))
+
+
+def nonzero_bbox_device(vol: DeviceVolume) -> DeviceVolume:
+    """msk_nonzero_bbox: the record {d0, h0, w0, d1, h1, w1, count, 0} of the non-zero voxels of a float32 (x != 0) or int32
+    volume as eight int32 in a pooled device buffer (``free()`` hands it back); the upper corner is exclusive, an empty volume
+    gives zeros.  Holes do not change a bounding box, so this is the box of nnU-Net's hole-filled non-zero mask.  Nothing is
+    downloaded and nothing synchronises."""
+    if not isinstance(vol, DeviceVolume) or len(vol.shape) != 3:
+        raise TypeError("nonzero_bbox_device takes a 3-D DeviceVolume")
+    with _pooled_outputs(vol.dev, ((8,), np.int32)) as (box,):
+        vol.dev.call("msk_nonzero_bbox", C.c_void_p(vol.ptr), *vol.shape, _dt(vol), C.c_void_p(box.ptr))
+    return box
+
+
+def crop_to_nonzero_device(img: DeviceVolume, label=None):
+    """nnU-Net's crop_to_nonzero: ``(img, label, box)`` cut to the bounding box of the image's non-zero voxels (the existing
+    identity crop, msk_crop_resample3d at order 0) as NEW pooled volumes; the inputs stay the caller's.  ``box`` is the
+    downloaded record of nonzero_bbox_device as a host array.  SYNCHRONISES once: the 32-byte record is downloaded because the
+    output shape depends on it.  A volume without a non-zero voxel is returned whole (the same objects)."""
+    if label is not None and (not isinstance(label, DeviceVolume) or label.shape != img.shape):
+        raise TypeError("crop_to_nonzero_device takes a DeviceVolume of the image's shape as the label")
+    rec = nonzero_bbox_device(img)
+    box = rec.numpy()
+    rec.free()
+    if box[6] == 0:
+        return img, label, box
+    lo, ext = [int(v) for v in box[:3]], [int(v) for v in box[3:6] - box[:3]]
+    out = resized_crop_device(img, *lo, *ext, ext, 0)
+    try:
+        out_label = None if label is None else resized_crop_device(label, *lo, *ext, ext, 0)
+    except BaseException:
+        out.free()
+        raise
+    return out, out_label, box
+
+
+def fg_stats_device(vol: DeviceVolume, mask=None, mode="all", percentiles=(0.5, 99.5)) -> DeviceVolume:
+    """msk_fg_stats: the record FG_FIELDS of the valid voxels of a float32 volume (``mode`` 'all'; 'nonzero': x != 0, nnU-Net's
+    non-zero mask without its hole filling; 'mask': ``mask`` > 0, an int32 volume) as sixteen float64 in a pooled device buffer:
+    count, exact min / max, the float64 sums in msk_intensity_stats' fixed order, mean, std and the two ``percentiles`` by
+    numpy's default method, every field exact (tests/normalize_reference.py).  The workspace comes from the pool and goes back
+    to it.  Nothing is downloaded and nothing synchronises: clip_zscore_device reads the record on the device."""
+    _float_volume(vol, "fg_stats_device")
+    mm = _mask_mode(mode, mask)
+    if mask is not None:
+        _mask_volume(vol, mask, "fg_stats_device")
+    q = _percentile_pair(percentiles)
+    dev = vol.dev
+    nbytes = _workspace_bytes(dev, "msk_fg_stats_workspace", C.c_long(vol.size))
+    with _pooled_outputs(dev, ((16,), np.float64)) as (rec,), _pooled_scratch(dev, nbytes) as ws:
+        dev.call("msk_fg_stats", C.c_void_p(vol.ptr), C.c_void_p(mask.ptr) if mask is not None else None, C.c_long(vol.size), mm,
+                 C.c_double(q[0]), C.c_double(q[1]), C.c_void_p(ws), C.c_void_p(rec.ptr))
+    return rec
+
+
+def clip_zscore_device(vol: DeviceVolume, stats=None, lo=None, hi=None, mean=None, std=None, mask=None, mode="all", clip=True,
+                       zscore=True, outside=None, inplace=True) -> DeviceVolume:
+    """msk_clip_zscore: one streaming pass, in place (returns ``vol``) or into a new pooled volume: clip to [lo, hi], then
+    (x - mean) / max(std, 1e-8) as a multiplication by the float64 reciprocal.  The four values come from ``stats`` (a
+    fg_stats_device record: its percentiles, mean and std, read on the device, nothing synchronises) or are given (nnU-Net's CT
+    plan: dataset-level values).  ``clip`` / ``zscore`` switch the two steps; with ``outside`` set, a voxel that is not valid
+    under ``mode`` / ``mask`` becomes that value (nnU-Net: 0), otherwise it is transformed like every other voxel."""
+    _float_volume(vol, "clip_zscore_device")
+    mm = _mask_mode(mode, mask)
+    if mask is not None:
+        _mask_volume(vol, mask, "clip_zscore_device")
+    if stats is not None and (not isinstance(stats, DeviceVolume) or stats.dtype != np.float64 or stats.size != 16):
+        raise TypeError("clip_zscore_device takes a fg_stats_device record as stats")
+    p = _norm_params(stats, lo, hi, mean, std, clip, zscore)
+    flags = (NORM_CLIP if clip else 0) | (NORM_ZSCORE if zscore else 0) | (NORM_MASK_OUT if outside is not None else 0)
+    with _pooled_outputs(vol.dev, None if inplace else (vol.shape, vol.dtype)) as (out,):
+        out = vol if inplace else out
+        vol.dev.call("msk_clip_zscore", C.c_void_p(vol.ptr), C.c_void_p(mask.ptr) if mask is not None else None, C.c_long(vol.size),
+                     mm, C.c_void_p(stats.ptr) if stats is not None else None, p.ctypes.data_as(C.c_void_p) if p is not None else None,
+                     flags, C.c_float(0.0 if outside is None else float(outside)), C.c_void_p(out.ptr))
+    return out
+
+
+# The numpy host path: tests/normalize_reference.py's statement bit for bit, for callers that want no device.
+def _sort_keys(x):
+    b = x.view(np.uint32)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _unsort_keys(k):
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+def _valid_host(x, mm, mask):
+    if mm == 0:
+        return np.ones(x.size, bool)
+    if mm == 1:
+        return x != 0
+    m = np.ascontiguousarray(mask, np.int32).reshape(-1)
+    if m.size != x.size:
+        raise ValueError("the mask must have the volume's size")
+    return m > 0
+
+
+def fg_stats_host(image, mask=None, mode="all", percentiles=(0.5, 99.5)) -> np.ndarray:
+    """fg_stats_device's record computed in numpy, bit for bit the same: sixteen float64 (FG_FIELDS and a zero)"""
+    from .transforms.transform import _ordered_sum
+    mm = _mask_mode(mode, mask)
+    q = _percentile_pair(percentiles)
+    x = np.ascontiguousarray(image, np.float32).reshape(-1)
+    valid = _valid_host(x, mm, mask)
+    nv = int(np.count_nonzero(valid))
+    rec = np.zeros(16, np.float64)
+    if nv == 0:
+        return rec
+    s = _unsort_keys(np.sort(_sort_keys(x[valid]))).astype(np.float64)
+    d = np.where(valid, x.astype(np.float64), 0.0)
+    n64 = np.float64(nv)
+    rec[0], rec[1], rec[2] = n64, s[0], s[-1]
+    rec[3], rec[4] = _ordered_sum(d), _ordered_sum(d * d)
+    rec[5] = rec[3] / n64
+    rec[6] = np.sqrt(max(rec[4] / n64 - rec[5] * rec[5], np.float64(0.0)))
+    for t, qq in enumerate(q):
+        h = np.float64(nv - 1) * (np.float64(qq) / np.float64(100.0))
+        i = int(np.floor(h))
+        g = h - np.floor(h)
+        a, b = s[i], s[min(i + 1, nv - 1)]
+        dd = b - a
+        rec[7 + t] = b - dd * (np.float64(1.0) - g) if g >= 0.5 else a + dd * g
+        rec[9 + 3 * t:12 + 3 * t] = [a, b, g]
+    return rec
+
+
+def clip_zscore_host(image, stats=None, lo=None, hi=None, mean=None, std=None, mask=None, mode="all", clip=True, zscore=True,
+                     outside=None) -> np.ndarray:
+    """clip_zscore_device in numpy, bit for bit the same; ``stats`` is a fg_stats_host record"""
+    mm = _mask_mode(mode, mask)
+    p = _norm_params(stats, lo, hi, mean, std, clip, zscore)
+    if p is None:
+        p = np.array([stats[7], stats[8], stats[5], stats[6]], np.float64)
+    x = np.ascontiguousarray(image, np.float32)
+    y = x
+    if clip:
+        lo32, hi32 = np.float32(p[0]), np.float32(p[1])
+        y = np.where(y < lo32, lo32, y)
+        y = np.where(y > hi32, hi32, y)
+    if zscore:
+        inv = np.float32(np.float64(1.0) / max(p[3], np.float64(1e-8)))
+        y = (y - np.float32(p[2])).astype(np.float32) * inv
+    if outside is not None:
+        y = np.where(_valid_host(x.reshape(-1), mm, mask).reshape(x.shape), y, np.float32(outside))
+    return np.array(y, np.float32)
+
+
+def nonzero_bbox_host(volume) -> np.ndarray:
+    """nonzero_bbox_device's record in numpy: eight int32"""
+    v = np.asarray(volume)
+    if v.ndim != 3:
+        raise ValueError("expected a 3-D volume, got shape {}".format(v.shape))
+    nz = np.nonzero(v != 0)
+    box = np.zeros(8, np.int32)
+    if nz[0].size:
+        box[:3] = [c.min() for c in nz]
+        box[3:6] = [c.max() + 1 for c in nz]
+        box[6] = nz[0].size
+    return box
+
+
+def _zscore_settings(percentiles, mode):
+    """(percentiles of the record, clip on?, outside value) of a z-score call: outside the mask voxels become 0, as in nnU-Net"""
+    return (percentiles if percentiles is not None else (0.0, 100.0)), percentiles is not None, (None if mode == "all" else 0.0)
+
+
+def ct_normalize(image, lo, hi, mean, std, on_device=True):
+    """nnU-Net's CTNormalization with the plan's dataset-level values: clip to [lo, hi], then (x - mean) / max(std, 1e-8).
+    ``on_device`` False takes the numpy host path, which gives the same bits."""
+    if not on_device:
+        return clip_zscore_host(image, lo=lo, hi=hi, mean=mean, std=std)
+    _norm_params(None, lo, hi, mean, std, True, True)
+    return _on_host_array(lambda v: clip_zscore_device(v, lo=lo, hi=hi, mean=mean, std=std), image)
+
+
+def zscore_normalize(image, percentiles=None, mode="all", mask=None, on_device=True):
+    """nnU-Net's ZScoreNormalization per volume: mean and std of the valid voxels (``mode`` 'all', 'nonzero' or 'mask' with an
+    integer ``mask``), after clipping to the two ``percentiles`` of the valid voxels when they are given (MONAI's
+    ScaleIntensityRangePercentiles in front of NormalizeIntensity); with a mask the voxels outside it become 0.
+    ``on_device`` False takes the numpy host path, which gives the same bits."""
+    _mask_mode(mode, mask)
+    q, clip, outside = _zscore_settings(percentiles, mode)
+    _percentile_pair(q)
+    if not on_device:
+        rec = fg_stats_host(image, mask, mode, q)
+        return clip_zscore_host(image, stats=rec, mask=mask, mode=mode, clip=clip, outside=outside)
+    vol = upload(np.asarray(image, dtype=np.float32))
+    mvol = upload(np.asarray(mask).astype(np.int32)) if mask is not None else None
+    try:
+        rec = fg_stats_device(vol, mvol, mode, q)
+        out = clip_zscore_device(vol, stats=rec, mask=mvol, mode=mode, clip=clip, outside=outside).numpy()
+        rec.free()
+    finally:
+        vol.free()
+        if mvol is not None:
+            mvol.free()
+    return out
+
+
+def crop_to_nonzero(image, label=None, on_device=True):
+    """nnU-Net's crop_to_nonzero on host arrays -> (image, label, box): both cut to the bounding box of the image's non-zero
+    voxels, box = {d0, h0, w0, d1, h1, w1, count, 0}; an empty volume is returned whole.  ``on_device`` False slices in numpy."""
+    image = np.asarray(image)
+    if label is not None and np.asarray(label).shape != image.shape:
+        raise ValueError("the label must have the image's shape")
+    if on_device:
+        vol = upload(image)
+        rec = nonzero_bbox_device(vol)
+        box = rec.numpy()
+        rec.free()
+        vol.free()
+    else:
+        box = nonzero_bbox_host(image)
+    if box[6] == 0:
+        return image, label, box
+    sl = tuple(slice(int(a), int(b)) for a, b in zip(box[:3], box[3:6]))
+    return image[sl], (None if label is None else np.asarray(label)[sl]), box
+
+
+class ForegroundFingerprint:
+    """nnU-Net's dataset fingerprint, the exact part of it: per case the statistics of the image voxels under the label's
+    foreground (label > 0), gathered on the device; the records stay there until ``result()`` downloads them once.
+
+    Dataset-pooled percentiles are not a function of per-case records and are out of scope: a caller who wants them runs
+    fg_stats_device on a concatenated flat buffer of the cases' voxels."""
+
+    def __init__(self, percentiles=(0.5, 99.5)):
+        self.percentiles = tuple(_percentile_pair(percentiles))
+        self._records = []
+
+    def add(self, img_vol: DeviceVolume, label_vol: DeviceVolume):
+        """enqueue fg_stats_device with the label as the mask; nothing synchronises"""
+        self._records.append(fg_stats_device(img_vol, label_vol, "mask", self.percentiles))
+
+    def result(self):
+        """download the records (one synchronisation per call) -> a dict: pooled ``n``, ``min``, ``max``, ``mean`` and ``std``
+        from the n / sum / sumsq summed over the cases in float64 in case order, and the per-case records and percentiles"""
+        recs = np.stack([r.numpy() for r in self._records]) if self._records else np.zeros((0, 16), np.float64)
+        seen = recs[recs[:, 0] > 0]
+        n = s = ss = np.float64(0.0)
+        for r in recs:
+            n, s, ss = n + r[0], s + r[3], ss + r[4]
+        out = {"n": int(n), "records": recs, "percentiles": recs[:, 7:9].copy(), "min": None, "max": None, "mean": None, "std": None}
+        if n > 0:
+            mean = s / n
+            out.update(min=float(seen[:, 1].min()), max=float(seen[:, 2].max()), mean=float(mean),
+                       std=float(np.sqrt(max(ss / n - mean * mean, np.float64(0.0)))))
+        return out
+
+    def free(self):
+        for r in self._records:
+            r.free()
+        self._records = []
+
+
 def _upload(image, dev, pooled) -> DeviceVolume:
     dev = dev or get_device()
     a = np.asarray(image)
@@ -534,6 +835,33 @@ class _Chain:
 
     def max_normalize(self):
         max_normalize_device(self.vol)
+        return self
+
+    def crop_to_nonzero(self):
+        """cut to the bounding box of the non-zero voxels (crop_to_nonzero_device: one 32-byte download, the chain's only
+        synchronisation); the record stays in ``self.box``"""
+        out, _, self.box = crop_to_nonzero_device(self.vol)
+        if out is not self.vol:
+            old, self.vol = self.vol, out
+            old.free()
+        return self
+
+    def ct_normalize(self, lo, hi, mean, std):
+        """nnU-Net's CTNormalization with the plan's values, in place"""
+        clip_zscore_device(self.vol, lo=lo, hi=hi, mean=mean, std=std)
+        return self
+
+    def zscore(self, percentiles=None, mode="all"):
+        """nnU-Net's ZScoreNormalization of this volume, in place: statistics of all voxels or of the non-zero ones (outside
+        them the result is 0), after clipping to the two ``percentiles`` when given; the record never leaves the device"""
+        if mode not in ("all", "nonzero"):
+            raise ValueError("a chain z-scores over 'all' or 'nonzero' voxels, got {!r}".format(mode))
+        q, clip, outside = _zscore_settings(percentiles, mode)
+        rec = fg_stats_device(self.vol, None, mode, q)
+        try:
+            clip_zscore_device(self.vol, stats=rec, mode=mode, clip=clip, outside=outside)
+        finally:
+            rec.free()
         return self
 
     def tensor(self):

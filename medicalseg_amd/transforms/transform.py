@@ -219,10 +219,19 @@ class RandomResizedCrop3D:
         """transform.py:288-318: numpy's global RNG draws the box (3 uniforms, then 3 randints)."""
         crop = (np.random.uniform(low=self.scale[0], high=self.scale[1], size=3) * self.size).round().astype("int")
         if self.nonzero_mask:
-            lab = label.numpy() if _on_device(label) else label
-            nz = np.where(lab != 0)
-            lo = np.array([int(np.min(c)) for c in nz])
-            hi = np.array([int(np.max(c)) + 1 for c in nz])
+            if _on_device(label):
+                # the 32-byte record instead of the whole label; an empty label fails as np.min of nothing does on the host
+                from ..preprocess import nonzero_bbox_device
+                rec = nonzero_bbox_device(label)
+                box = rec.numpy()
+                rec.free()
+                if box[6] == 0:
+                    raise ValueError("zero-size array to reduction operation minimum which has no identity")
+                lo, hi = box[:3].astype(int), box[3:6].astype(int)
+            else:
+                nz = np.where(label != 0)
+                lo = np.array([int(np.min(c)) for c in nz])
+                hi = np.array([int(np.max(c)) + 1 for c in nz])
         else:
             lo = np.zeros(3, dtype=int)
             hi = np.array(img.shape[:3])
