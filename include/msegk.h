@@ -676,6 +676,45 @@ int msk_topk_ce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int 
 int msk_topk_ce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const float* weights,
                     const void* workspace, const double* record, float coef, int accumulate, msk_tensor dz);
 
+/* ---- boundary loss on signed distance maps built on the device (BoundaryLoss, DiceBoundaryLoss: Kervadec et al., MIDL 2019,
+ *      the BDLoss / DC_and_BD_loss of the nnU-Net loss collections; the reference has no such loss, so every entry cites
+ *      tests/boundary_reference.py, the statement) ---- */
+/* Bytes of workspace for one volume of d x h x w voxels (every extent in 1 .. MSK_EDT_MAX_EXTENT): its two float64 distance
+ * fields, each rounded up to 256 bytes.  Needs no context and no GPU.  (tests/boundary_reference.py: signed_distance)          */
+int msk_sdf_workspace(int d, int h, int w, size_t* bytes);
+/* Signed distance maps of the int32 labels [n][d][h][w] (DEVICE, not modified) for the classes whose bit is set in class_mask.
+ * phi (DEVICE, 16-byte aligned) is class-planar: plane (s * |S| + j) holds the V = d h w floats of sample s and the j-th set bit
+ * c.  With pos = (label == c) (everything else is outside, 255 and labels beyond the class range included),
+ *   d_out = sqrt(msk_edt3d's dist2 to the features {== c}),  d_in = sqrt(dist2 to the features {!= c}),   both float64,
+ *   phi = d_out outside the class, 1 - d_in inside it (a voxel with d_in = 1 gets +0.0), 0 where the squared distance is +inf
+ *   (the class is absent from the volume or fills it),   rounded once to float32.
+ * Bit for bit tests/boundary_reference.py: signed_distance, which equals Kervadec's one_hot2dist wherever the class is present
+ * and does not fill the volume.  Per (sample, class) two exact transforms (the passes of msk_edt3d; the complement comes from a
+ * complemented x pass, no mask volume is written) and one compose pass: seven launches, in the two fields of the workspace
+ * (DEVICE, 16-byte aligned, workspace_bytes >= msk_sdf_workspace(d, h, w)), which are reused from one to the next.  spacing
+ * (HOST, nullable = 1, 1, 1): sz, sy, sx, in msk_edt3d's range; the constant 1 is Kervadec's whatever the spacing.  No atomics,
+ * nothing is downloaded, nothing synchronises.  n d h w < 2^31.                                                                */
+int msk_label_sdf(msk_ctx* ctx, const int32_t* labels, int n, int d, int h, int w, uint64_t class_mask,
+                  const double* spacing /* HOST, nullable */, void* workspace, size_t workspace_bytes, float* phi);
+/* Boundary loss of logits [N,D,H,W,C] (ld >= C, 2 <= C <= 64) against the maps phi of msk_label_sdf for the same class_mask S.
+ * A voxel is valid when its label is in [0, C) and is not ignore_index (the top-k loss's rule); p = softmax(z);
+ *   t_c(v) = p_c(v) phi_c(v) for c in S at valid v, else 0;   L = sum t / (n_valid |S|),   A = sum |t| / (n_valid |S|),
+ *   L_c = sum_v t_c(v) / n_valid.
+ * out (DEVICE, 2 + C floats) = {L, A, L_c for every class (0 outside S)}; stats (DEVICE, 3 + C doubles) = {n_valid, sum t,
+ * sum |t|, sum t_c per class}; n_valid == 0: L = A = L_c = 0.  fp32 per-thread sums, one record per workgroup, merged by one
+ * workgroup in float64 in a fixed order: no float atomics, two calls give the same bits.  Two launches.
+ * (tests/boundary_reference.py: boundary_loss)                                                                                 */
+int msk_boundary_loss_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, uint64_t class_mask,
+                          const float* phi, float* out, double* stats);
+/* dlogits_k(v) (+)= coef p_k(v) ([k in S] phi_k(v) - sum_{c in S} t_c(v)) / (n_valid |S|) at the valid voxels (classes outside S
+ * do get a gradient), n_valid read from the forward's stats on the device.  An invalid voxel gets exactly 0, or is left as it is
+ * when accumulate != 0.  One launch.  (tests/boundary_reference.py: boundary_loss)
+ * Argument errors of all four, reported before any launch: C outside 2..64, an empty class_mask or one with a bit >= C, an extent
+ * outside 1..MSK_EDT_MAX_EXTENT, N V >= 2^31, a null pointer, phi or the workspace not 16-byte aligned, a workspace that is too
+ * small, spacing outside msk_edt3d's range, dlogits overlapping logits or phi, a dlogits of another shape.                      */
+int msk_boundary_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, uint64_t class_mask,
+                          const float* phi, const double* stats, float coef, int accumulate, msk_tensor dlogits);
+
 /* ---- foreground statistics, percentile clipping, z-scoring and the non-zero bounding box (nnU-Net's crop_to_nonzero,
  *      CTNormalization, ZScoreNormalization; preprocess.fg_stats_device / clip_zscore_device / nonzero_bbox_device;
  *      tests/normalize_reference.py is the statement) ---- */

@@ -163,6 +163,10 @@ SIGNATURES = {
     "msk_fg_stats": (_i, [_vp, _vp, _vp, C.c_long, _i, _d, _d, _vp, _vp]),
     "msk_clip_zscore": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp, _i, _f, _vp]),
     "msk_nonzero_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "msk_sdf_workspace": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "msk_label_sdf": (_i, [_vp, _vp, _i, _i, _i, _i, _u64, _vp, _vp, _sz, _vp]),
+    "msk_boundary_loss_fwd": (_i, [_vp, _T, _vp, _i, _u64, _vp, _vp, _vp]),
+    "msk_boundary_loss_bwd": (_i, [_vp, _T, _vp, _i, _u64, _vp, _vp, _f, _i, _T]),
     "msk_sgd_momentum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_eager": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f]),
     "msk_sgd_momentum_finish": (_i, [_vp]),

@@ -187,6 +187,9 @@ void msk_small_pack_freed(msk_ctx* ctx, const void* p, size_t bytes);
 int msk_small_prepack(msk_ctx* ctx, const void* p, size_t bytes);        // p == nullptr: every stale row in use
 void msk_small_pack_free(msk_ctx* ctx);
 int msk_dp_wait_impl(msk_ctx* ctx);
+// msk_edt3d's checks and passes (msk_edt.hip); complement != 0: the features are {vol != cls} (msk_label_sdf)
+int msk_edt_field(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, int complement,
+                  const double* spacing, double* dist2);
 // merge of the [nb][4][C] partial sums of a join backward fused with its unit (msk_elementwise.hip: the merge launch of
 // msk_add_act_join_bwd_pg): all four quantities are stored to unit_sums, which needs 4*C floats; 0..2 are also added to the
 // (nullable) parameter gradients, 3 to dalpha

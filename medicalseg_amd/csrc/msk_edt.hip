@@ -3,7 +3,8 @@
 //
 // Specification (utils/metric.py states it in numpy; the kernels return exactly these bits):
 //   features F = {vol == cls}, or its surface S = the voxels of F with a face neighbour outside F (beyond the volume's
-//   edge counts as outside);  wx, wy, wz = the squared spacings, rounded once;
+//   edge counts as outside), or -- msk_edt_field with `complement`, for the signed distance maps of msk_loss_boundary.hip --
+//   the complement {vol != cls};  wx, wy, wz = the squared spacings, rounded once;
 //   dist2(v) = min over u in F of fl(fl(fl(wx dx^2) + fl(wy dy^2)) + fl(wz dz^2)),  +inf when F is empty,
 // every fl one float64 rounding, no fused multiply-add (contraction is switched off for this file and the kernels'
 // code objects hold no v_fma_f64).  Rounding is monotone, so the minimum separates:
@@ -41,10 +42,12 @@ constexpr int kTileBytes = 32768;
 struct Vol {
   const int32_t* p;
   int d, h, w, cls, surface;
+  int complement;   // the features are {vol != cls} (msk_edt_field for msk_label_sdf; never with surface)
 };
 
 // is voxel (z, y, x), whose value is v, a feature?
 __device__ __forceinline__ bool edt_feature(const Vol& g, long i, int z, int y, int x, int v) {
+  if (g.complement) return v != g.cls;
   if (v != g.cls) return false;
   if (!g.surface) return true;
   if (x == 0 || x == g.w - 1 || y == 0 || y == g.h - 1 || z == 0 || z == g.d - 1) return true;
@@ -247,12 +250,13 @@ int launch_line(msk_ctx* ctx, const char* tag, double* g, int L, long lstride, i
 
 }  // namespace
 
-extern "C" {
-
-int msk_edt3d(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, const double* spacing,
-              double* dist2) {
+// the checks and the three passes of msk_edt3d; complement != 0: the features are {vol != cls} (msk_label_sdf of
+// msk_loss_boundary.hip: the distance to the nearest voxel NOT of the class), surface_only must be 0 then
+int msk_edt_field(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, int complement,
+                  const double* spacing, double* dist2) {
   if (int rc = check_volume(ctx, vol, d, h, w)) return rc;
   MSK_REQUIRE(ctx, dist2 != nullptr && (((uintptr_t)dist2) & 7) == 0, "dist2 must be an 8-byte aligned device pointer");
+  MSK_REQUIRE(ctx, !(complement && surface_only), "the complemented transform has no surface form");
   double wgt[3] = {1.0, 1.0, 1.0};
   if (spacing != nullptr) {
     for (int a = 0; a < 3; ++a) {
@@ -261,7 +265,7 @@ int msk_edt3d(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, in
       MSK_REQUIRE(ctx, spacing[a] > 0.0 && wgt[a] >= 1e-300 && wgt[a] <= 1e300, "spacing must be positive, its square within [1e-300, 1e300]");
     }
   }
-  const Vol g{vol, d, h, w, cls, surface_only ? 1 : 0};
+  const Vol g{vol, d, h, w, cls, surface_only ? 1 : 0, complement ? 1 : 0};
   {
     msk_launch_scope ls(ctx, "edt_x");
     hipLaunchKernelGGL(edt_x_k, dim3((unsigned)grid_for(ctx, (long)d * h, kWaves)), dim3(kThreads), 0, ctx->stream, g, wgt[2], dist2);
@@ -271,11 +275,18 @@ int msk_edt3d(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, in
   return launch_line(ctx, "edt_z", dist2, d, (long)h * w, h, w, w, wgt[0]);
 }
 
+extern "C" {
+
+int msk_edt3d(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, const double* spacing,
+              double* dist2) {
+  return msk_edt_field(ctx, vol, d, h, w, cls, surface_only, 0, spacing, dist2);
+}
+
 int msk_surface_count(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, unsigned long long* count) {
   if (int rc = check_volume(ctx, vol, d, h, w)) return rc;
   MSK_REQUIRE(ctx, count != nullptr && (((uintptr_t)count) & 7) == 0, "count must be an 8-byte aligned device pointer");
   MSK_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
-  const Vol g{vol, d, h, w, cls, 1};
+  const Vol g{vol, d, h, w, cls, 1, 0};
   msk_launch_scope ls(ctx, "surface_count");
   hipLaunchKernelGGL(surface_count_k, dim3((unsigned)grid_for(ctx, (long)d * h * w, 4L * kThreads)), dim3(kThreads), 0, ctx->stream,
                      g, count);
@@ -291,7 +302,7 @@ int msk_surface_gather(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, in
               "out must be an 8-byte aligned device pointer of `capacity` >= 0 doubles");
   MSK_REQUIRE(ctx, count != nullptr && (((uintptr_t)count) & 7) == 0, "count must be an 8-byte aligned device pointer");
   MSK_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
-  const Vol g{vol, d, h, w, cls, 1};
+  const Vol g{vol, d, h, w, cls, 1, 0};
   msk_launch_scope ls(ctx, "surface_gather");
   hipLaunchKernelGGL(surface_gather_k, dim3((unsigned)grid_for(ctx, (long)d * h * w, 4L * kThreads)), dim3(kThreads), 0, ctx->stream,
                      g, dist2, out, capacity, count);

@@ -5,3 +5,4 @@ from .mixes_losses import MixedLoss
 from .binary_cross_entropy_loss import BCELoss
 from .region_losses import DiceCELoss, FocalLoss, SoftDiceLoss, TverskyLoss
 from .topk_losses import DiceTopKLoss, TopKLoss
+from .boundary_losses import BoundaryLoss, DiceBoundaryLoss

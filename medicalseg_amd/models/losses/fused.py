@@ -238,6 +238,47 @@ class TopKNode(Node):
                       accumulate, dz.msk())
 
 
+class BoundaryNode(Node):
+    """Boundary loss (the 'boundary' term, out[0]; out[1] is the mean of the absolute terms, out[2:] the per-class means):
+    msk_label_sdf, then msk_boundary_loss_fwd / msk_boundary_loss_bwd.  `settings` is (ignore_index, class_mask, spacing):
+    class_mask the bits of the classes whose signed distance maps count, spacing a (sz, sy, sx) tuple or None.  The maps are
+    built on the device from THIS node's labels (a native deep-supervision head: its own level of the label pyramid) once per
+    forward; they and the transform's workspace come from the activation arena and live until the next model forward, like the
+    other records.  With several ranks the sums are those of this rank's batch."""
+    SLOTS = {"boundary": 0}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.ignore_index, self.class_mask, self.spacing = settings
+        self.phi_ptr = None
+        self.ws_ptr = None
+        self.ws_bytes = 0
+
+    def stats_doubles(self):
+        return 3 + self.C
+
+    def _args(self):
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(self.ignore_index), C.c_uint64(self.class_mask),
+                C.c_void_p(self.phi_ptr))
+
+    def _forward(self):
+        t = self.logits
+        if self.phi_ptr is None:
+            nbytes = C.c_size_t(0)
+            if self.dev.lib.msk_sdf_workspace(t.d, t.h, t.w, C.byref(nbytes)) != 0:
+                raise ValueError("msk_sdf_workspace refused a volume of %d x %d x %d" % (t.d, t.h, t.w))
+            planes = t.n * bin(self.class_mask).count("1")
+            self.phi_ptr = self.dev.arena.alloc(planes * t.d * t.h * t.w * 4)
+            self.ws_ptr, self.ws_bytes = self.dev.arena.alloc(nbytes.value), nbytes.value
+        spacing = None if self.spacing is None else (C.c_double * 3)(*self.spacing)
+        self.dev.call("msk_label_sdf", C.c_void_p(self.labels.ptr), t.n, t.d, t.h, t.w, C.c_uint64(self.class_mask), spacing,
+                      C.c_void_p(self.ws_ptr), C.c_size_t(self.ws_bytes), C.c_void_p(self.phi_ptr))
+        self.dev.call("msk_boundary_loss_fwd", *self._args(), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef, _, accumulate, dz):
+        self.dev.call("msk_boundary_loss_bwd", *self._args(), C.c_void_p(self.stats_ptr), C.c_float(coef), accumulate, dz.msk())
+
+
 _CACHE = {}     # kind -> {key: node}
 
 
@@ -258,7 +299,7 @@ def node_for(kind, logits: Tensor, labels, settings=()):
 
 
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce' | 'topk'): the float node.slot(which) of the node's
+    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce' | 'topk' | 'boundary'): the float node.slot(which) of the node's
     record.  Values stay on the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 

@@ -579,6 +579,46 @@ def edt_squared(x, spacing=None, cls=1, surface_only=False):
     return out
 
 
+def signed_distance(x, cls=1, spacing=None):
+    """Signed distance map of class ``cls`` in the label volume ``x`` (Kervadec's one_hot2dist; tests/boundary_reference.py
+    is the statement): the distance to the class outside it, ``1 -`` the distance to its complement inside it, 0 where the
+    class is absent or fills the volume; float64 distances from edt_squared, rounded once to float32.
+
+    numpy input: a [D, H, W] label array, returns a float32 array.  Device input (int32 ``IntTensor`` [1, 1, D, H, W] /
+    [1, D, H, W] or 3-D ``DeviceVolume``): one msk_label_sdf call; returns a float32 ``DeviceVolume`` holding the same
+    bits.  Freeing the transform's workspace waits for the stream (the loss keeps its workspace in the arena and does not)."""
+    if not _is_device(x):
+        lab = np.asarray(x)
+        if lab.ndim != 3:
+            raise ValueError("expected a [D, H, W] label volume, got shape {}".format(lab.shape))
+        pos = lab == cls
+        with np.errstate(invalid="ignore"):
+            d_out = np.sqrt(_edt_squared_host(pos, spacing))
+            d_in = np.sqrt(_edt_squared_host(~pos, spacing))
+            phi = np.where(pos, 1.0 - d_in, d_out)
+        return np.where(np.isfinite(phi), phi, 0.0).astype(np.float32)
+    import ctypes as C
+    from ..preprocess import DeviceVolume
+    if not 0 <= int(cls) <= 63:
+        raise ValueError("signed_distance: device volumes take classes 0 .. 63, got {}".format(cls))
+    dev, ptr, (d, h, w) = _device_volume(x, "signed_distance")
+    sp = _c_spacing(spacing)
+    nbytes = C.c_size_t(0)
+    if dev.lib.msk_sdf_workspace(d, h, w, C.byref(nbytes)) != 0:
+        raise ValueError("msk_sdf_workspace refused a volume of {} x {} x {}".format(d, h, w))
+    ws = dev.malloc(nbytes.value)
+    out = DeviceVolume(dev, dev.malloc(4 * d * h * w), (d, h, w), np.float32)
+    try:
+        dev.call("msk_label_sdf", C.c_void_p(ptr), 1, d, h, w, C.c_uint64(1 << int(cls)), sp, C.c_void_p(ws),
+                 C.c_size_t(nbytes.value), C.c_void_p(out.ptr))
+    except Exception:
+        out.free()
+        raise
+    finally:
+        dev.free(ws)      # msk_free waits for the stream: the transform is done with it
+    return out
+
+
 class SurfaceDistances:
     """The two directed multisets of SQUARED surface distances of one class, sorted ascending: ``d2_pl`` (from the
     prediction's surface voxels to the label's surface) and ``d2_lp`` (the other way).  Metrics follow medpy and are
