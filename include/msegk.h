@@ -143,7 +143,9 @@ int msk_prof_report(msk_ctx* ctx, char* buf, int buflen, int* len);
  *   per CU targeted by the split-K of the direct / Winograd weight-gradient kernels; "wgrad_wino_rounds" 0 = pick the
  *   split count that fills whole waves of resident workgroups, the default) */
 int msk_set_option(msk_ctx* ctx, const char* key, int value);
-/* effective value of "dp_mode" (after MSEGK_DP_MODE and msk_dp_init's fall-backs), "conv_split", "wgrad_async", "world", "rank" */
+/* effective value of "dp_mode" (after MSEGK_DP_MODE and msk_dp_init's fall-backs), "conv_split", "wgrad_async", "world", "rank",
+ * "num_cu", "scalar_ring_served"; and the launch geometry of the elementwise kernels as it stands: "ew_cap", "reduce_cap",
+ * "reduce_vpl", "dense12" (what a caller that changes them puts back) */
 int msk_get_option(msk_ctx* ctx, const char* key, int* value);
 
 /* ---- layout at the boundary ------------------------------------------------ */

@@ -176,6 +176,7 @@ void msk_set_dense12(int v);           // option "dense12" (msk_elementwise.hip)
 void msk_set_reduce_vpl(int v);
 void msk_set_reduce_vpl_site(int v);   // option "reduce_vpl_site"          // option "reduce_vpl"
 void msk_set_ew_caps(int ew, int red);   // msk_elementwise.hip tuning knobs
+int msk_get_ew_option(const char* key, int* value);   // "ew_cap", "reduce_cap", "reduce_vpl", "dense12" as they stand: 1 = known key
 // caller memory that may hold convolution weights was (or is about to be) written / freed: derived forms are stale
 void msk_weights_changed_impl(msk_ctx* ctx, const void* p, size_t bytes);
 void msk_weights_freed_impl(msk_ctx* ctx, const void* p, size_t bytes);  // msk_free: drop the rows inside [p, p + bytes)

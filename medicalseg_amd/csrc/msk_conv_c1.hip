@@ -267,7 +267,7 @@ conv_c1_h2_k(C1HArgs ha) {
   __syncthreads();
   wm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   const float sx = wbf_scale_of(ha.x_amax), sw = wbf_scale_from(wm);
-  const float osc = 1.f / (sx * sw);
+  const wbf_unscale osc = wbf_unscale_of(sx, sw);
 
   // A fragments (weights): lane (row li = output channel of the tile, K group lk) holds taps 32 s + 8 lk .. + 7
   uint4 wh[KSTEPS][NT], wl[KSTEPS][NT];
@@ -389,7 +389,7 @@ conv_c1_h2_k(C1HArgs ha) {
               if (co >= a.CN) continue;
               float v[4];
 #pragma unroll
-              for (int j = 0; j < 4; ++j) v[j] = fmaf(acc[c][nt][j], osc, bq[nt][j]);
+              for (int j = 0; j < 4; ++j) v[j] = fmaf(acc[c][nt][j] * osc.r0, osc.r1, bq[nt][j]);
               if (a.stat_partial) {
                 if (cnt == 0.f) {
 #pragma unroll

@@ -304,7 +304,7 @@ conv_foldn_h2_k(FNH2Args a) {
   const int d_begin = seg * a.seg_len;
   const int d_end = min(a.D, d_begin + a.seg_len);
   const float sx = wbf_scale_of(a.x_amax);
-  const float osc = 1.f / (sx * wbf_scale_of(a.w_amax));
+  const wbf_unscale osc = wbf_unscale_of(sx, wbf_scale_of(a.w_amax));
 
   // staging map: 8 consecutive lanes fetch the quads of one voxel = its whole 128-byte line
   const __amdgpu_buffer_rsrc_t sres = __builtin_amdgcn_make_buffer_rsrc((void*)a.src, 0, a.src_bytes, 0x00020000);
@@ -415,7 +415,7 @@ conv_foldn_h2_k(FNH2Args a) {
         const int gh = h0 + r, gw = w0 + pw;
         if (co < a.CN && gh < a.H && gw < a.W) {
           const int k = pos * 4 + co;
-          float v = ((red[0][k] + red[1][k]) + (red[2][k] + red[3][k])) * osc + (a.bias ? a.bias[co] : 0.f);
+          float v = ((red[0][k] + red[1][k]) + (red[2][k] + red[3][k])) * osc.r0 * osc.r1 + (a.bias ? a.bias[co] : 0.f);
           float* o = a.dst + ((((long)n * a.D + d) * a.H + gh) * a.W + gw) * a.dld + co;
           if (a.accumulate) v += *o;
           if (a.prelu && v < 0.f) v *= a.prelu[co];

@@ -264,7 +264,7 @@ conv_tk_h2_k(TKH2Args a) {
   const int d_begin = seg * a.seg_len;
   const int d_end = min(a.D, d_begin + a.seg_len);
   const float sx = wbf_scale_of(a.x_amax);
-  const float osc = 1.f / (sx * wbf_scale_of(a.w_amax));
+  const wbf_unscale osc = wbf_unscale_of(sx, wbf_scale_of(a.w_amax));
   constexpr int ZERO = RING * SLOT;
   if (tid == 0) lds[ZERO] = make_uint2(0u, 0u);
 
@@ -359,7 +359,7 @@ conv_tk_h2_k(TKH2Args a) {
     float du[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float dv = acc[r][nt][j] * osc;
+      const float dv = acc[r][nt][j] * osc.r0 * osc.r1;
       float t = fmaf(xv[j], sc[j], sf[j]);
       const float tin = t;
       if (!(t > 0.f)) t *= ai[j];
@@ -469,7 +469,7 @@ conv_tk_h2_k(TKH2Args a) {
           float* o = a.dst + ((((long)n * a.D + d) * a.H + gh) * a.W + gw) * a.dld + 4 * lk;
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt) {
-            float4 v = make_float4(acc[r][nt][0] * osc, acc[r][nt][1] * osc, acc[r][nt][2] * osc, acc[r][nt][3] * osc);
+            float4 v = make_float4(acc[r][nt][0] * osc.r0 * osc.r1, acc[r][nt][1] * osc.r0 * osc.r1, acc[r][nt][2] * osc.r0 * osc.r1, acc[r][nt][3] * osc.r0 * osc.r1);
             float4* op = reinterpret_cast<float4*>(o + 16 * nt);
             if (a.accumulate) {
               const float4 e = *op;

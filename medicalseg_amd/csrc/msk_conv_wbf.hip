@@ -1643,7 +1643,7 @@ wbf_gemm_fused_k(FusedArgs f) {
   if constexpr (SH == 16) {
     // epilogue of the 16 x 16 tile map: a lane owns TWO output channels (l16 and 16 + l16) and, of each, NS16 x 4 positions
     // (rows 4 kq .. 4 kq + 3 of every sub-fragment) x 4 W outputs
-    const float osc = f.scaled ? 1.f / (wbf_scale_of(f.in_amax) * wbf_scale_of(f.w_amax)) : 1.f;
+    const wbf_unscale osc = f.scaled ? wbf_unscale_of(wbf_scale_of(f.in_amax), wbf_scale_of(f.w_amax)) : wbf_unscale{1.f, 1.f};
     const long vox0 = ((long)n * f.dvn + (long)(4 * t) * f.dvw) * f.dld;
     const long wst = (long)f.dvw * f.dld;
     const bool split_st = f.st_lo != nullptr;
@@ -1685,7 +1685,7 @@ wbf_gemm_fused_k(FusedArgs f) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             if (i >= wlim) break;
-            float r = fmaf(yo16[i][s][ct][jj], osc, bv);
+            float r = fmaf(yo16[i][s][ct][jj] * osc.r0, osc.r1, bv);
             if (f.accumulate) r += old[jj][i];
             if (f.prelu) r = r > 0.f ? r : sl * r;
             if (split_st) sbase[((op[jj] - obase) >> 1) + i * swst] = r;
@@ -1751,7 +1751,7 @@ wbf_gemm_fused_k(FusedArgs f) {
   // epilogue: y = yo / (operand scales) + bias [+ dst] [PReLU]; a lane owns ONE output channel (column li of the MFMA
   // result) and MR x 16 positions x 4 W outputs of it
   const int co = wn * 32 + li;
-  const float osc = f.scaled ? 1.f / (wbf_scale_of(f.in_amax) * wbf_scale_of(f.w_amax)) : 1.f;
+  const wbf_unscale osc = f.scaled ? wbf_unscale_of(wbf_scale_of(f.in_amax), wbf_scale_of(f.w_amax)) : wbf_unscale{1.f, 1.f};
   const float bv = f.bias ? f.bias[co] : 0.f;
   const float sl = f.prelu ? f.prelu[co] : 1.f;
   float* obase = f.dst + ((long)n * f.dvn + (long)(4 * t) * f.dvw) * f.dld + co;
@@ -1792,7 +1792,7 @@ wbf_gemm_fused_k(FusedArgs f) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (i >= wlim) break;
-          float r = fmaf(yo[i][mr][jq * 4 + jj], osc, bv);
+          float r = fmaf(yo[i][mr][jq * 4 + jj] * osc.r0, osc.r1, bv);
           if (f.accumulate) r += old[jj][i];
           if (f.prelu) r = r > 0.f ? r : sl * r;
           if ((WBF_PROBE & 8) && r != 12345.678f) continue;   // probe: no stores (the value still has to be computed)
@@ -1895,7 +1895,7 @@ wbf_tout_k(ToutArgs a) {
   const int c4n = a.CN >> 2;
   float sk[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   float cnt = 0.f;
-  const float osc = a.scaled ? 1.f / (wbf_scale_of(a.in_amax) * wbf_scale_of(a.w_amax)) : 1.f;  // power of two: exact
+  const wbf_unscale osc = a.scaled ? wbf_unscale_of(wbf_scale_of(a.in_amax), wbf_scale_of(a.w_amax)) : wbf_unscale{1.f, 1.f};  // powers of two: exact
   const long total = (long)a.N * a.T * a.LD * a.LH * c4n;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int c4 = (int)(idx % c4n);
@@ -1948,7 +1948,7 @@ wbf_tout_k(ToutArgs a) {
     for (int i = 0; i < 4; ++i) {
       if (4 * t + i < a.LW) {
         float4* op = reinterpret_cast<float4*>(o + (long)i * a.dvw * a.dld);
-        float4 r = make_float4(fmaf(yx[i], osc, bv.x), fmaf(yy[i], osc, bv.y), fmaf(yz[i], osc, bv.z), fmaf(yw[i], osc, bv.w));
+        float4 r = make_float4(fmaf(yx[i] * osc.r0, osc.r1, bv.x), fmaf(yy[i] * osc.r0, osc.r1, bv.y), fmaf(yz[i] * osc.r0, osc.r1, bv.z), fmaf(yw[i] * osc.r0, osc.r1, bv.w));
         if (a.accumulate) {
           const float4 e = old4[i];
           r.x += e.x; r.y += e.y; r.z += e.z; r.w += e.w;

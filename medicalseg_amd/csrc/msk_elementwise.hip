@@ -1875,7 +1875,8 @@ const float* msk_absmax(msk_ctx* ctx, const float* x, int ld, int C, long voxels
   }
   msk_launch_scope ls(ctx, tag);
   long ab = (voxels * C / 4 + kThreads - 1) / kThreads;
-  if (ab > 8L * ctx->num_cu) ab = 8L * ctx->num_cu;
+  const long ab_cap = 2L * g_ew_cap * ctx->num_cu;   // 8 blocks per CU at the product's "ew_cap" 4; the option shrinks this grid with the others (tests reach the unrolled loops)
+  if (ab > ab_cap) ab = ab_cap;
   if (ab < 1) ab = 1;
   hipLaunchKernelGGL(absmax_k, dim3((unsigned)ab), dim3(kThreads), 0, ctx->stream, x, ld, C, voxels,
                      (unsigned*)slot);
@@ -1966,4 +1967,12 @@ void msk_set_reduce_vpl_site(int v) { if (v >= 0 && v < 4000) g_reduce_vpl_site[
 void msk_set_ew_caps(int ew, int red) {
   if (ew > 0) g_ew_cap = ew;
   if (red > 0) g_reduce_cap = red;
+}
+int msk_get_ew_option(const char* key, int* value) {
+  if (strcmp(key, "ew_cap") == 0) *value = g_ew_cap;
+  else if (strcmp(key, "reduce_cap") == 0) *value = g_reduce_cap;
+  else if (strcmp(key, "reduce_vpl") == 0) *value = g_reduce_vpl;
+  else if (strcmp(key, "dense12") == 0) *value = g_dense12;
+  else return 0;
+  return 1;
 }

@@ -63,7 +63,7 @@ __device__ __forceinline__ uint4 wbf_hi_down(uint4 h) {
 // the second (msk_conv3d_bwd_bnact: the weights have not changed since the forward pass).
 constexpr int kWbfXformHeader = 512;  // two amax arrays: max |x| and max |w| the forward pass scaled by
 // Power-of-two scale of a tensor from (an upper bound of) its max |value| on the DEVICE (no host round trip): amax * scale
-// lands in [2^9, 2^10), the Winograd transforms amplify by <= 21.25, fp16 overflows at 65504 = 2^16.  NULL / 0 / inf -> 1.
+// lands in [2^9, 2^10) (for amax >= 2^-117; below that the scale stops at 2^126, wbf_scale_from), the Winograd transforms amplify by <= 21.25, fp16 overflows at 65504 = 2^16.  NULL / 0 / inf -> 1.
 // An "amax" is an array of kWbfAmaxWays floats whose maximum counts: producers spread their atomics over the ways by block
 // index (a thousand blocks updating ONE address cost as much as the pass they ride on), consumers take the max of all.
 constexpr int kWbfAmaxWays = 64;
@@ -81,7 +81,27 @@ __device__ __forceinline__ float wbf_scale_from(float a) {
   if (!(a > 0.f) || !(a < 3.0e38f)) return 1.f;
   int e;
   (void)frexpf(a, &e);  // a = m * 2^e, m in [0.5, 1)
-  return ldexpf(1.f, 10 - e);
+  // at most 2^126: the rule gives 2^128 = inf from a < 2^-118 on (a normal float), and the reciprocal of 2^127 is subnormal.
+  // The limit takes effect for a < 2^-117: such maxima land under 2^9 in scaled units, down to the smallest subnormal float
+  // (2^-149 -> 2^-23) still above the 2^-24 of the maximum that the scaled low piece keeps normal.
+  return ldexpf(1.f, 10 - e > 126 ? 126 : 10 - e);
+}
+// The output stages divide their sums by the two operand scales.  The product of the scales is never formed: it overflows
+// fp32 when the operands are small (max |x| < 2^-105 against weights of max 0.1: 2^115 * 2^13), and its reciprocal is then 0.
+// The two reciprocals (powers of two with exponents in [-126, 118]: normal floats) are applied one after the other, the smaller
+// first, so that the intermediate lies between the sum and the result or below both -- it cannot overflow, and it is exact
+// (the same bits as one multiplication by the product) unless it falls under 2^-126.  That can happen where the single
+// multiplication stayed normal only when one reciprocal exceeds 1 (an operand with a maximum >= 2^10 against a tiny one) and
+// only for sums 2^-126 / r0 below the largest: elements near the flush-to-zero floor of the result.
+struct wbf_unscale {
+  float r0, r1;  // r0 <= r1
+};
+__device__ __forceinline__ wbf_unscale wbf_unscale_of(float s0, float s1) {
+  const float a = 1.f / s0, b = 1.f / s1;
+  wbf_unscale u;
+  u.r0 = a < b ? a : b;
+  u.r1 = a < b ? b : a;
+  return u;
 }
 __device__ __forceinline__ float wbf_scale_of(const float* amax) {
   if (!amax) return 1.f;

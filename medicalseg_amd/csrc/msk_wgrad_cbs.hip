@@ -352,7 +352,7 @@ wgrad_cbs_h2_k(WGrad g, int ntiles, int tiles_d, int tiles_h, int tiles_w, float
   }
 
   // the four wavefronts' sums meet in LDS in a fixed order; D[row = 4*kq + j][col = r]
-  const float ix = 1.f / sx, iy = 1.f / sy;
+  const wbf_unscale us = wbf_unscale_of(sx, sy);   // msk_wbf.h: the reciprocals one after the other, the smaller first
   float* red = reinterpret_cast<float*>(ysd);
   for (int wv = 0; wv < 4; ++wv) {
     __syncthreads();
@@ -369,7 +369,7 @@ wgrad_cbs_h2_k(WGrad g, int ntiles, int tiles_d, int tiles_h, int tiles_w, float
         for (int c = 0; c < 2; ++c)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            red[((grp * RT + t) * 16 + 4 * kq + j) * 32 + c * 16 + r] = prev[c][j] + acc[t][c][j] * ix * iy;
+            red[((grp * RT + t) * 16 + 4 * kq + j) * 32 + c * 16 + r] = prev[c][j] + acc[t][c][j] * us.r0 * us.r1;
       }
     }
   }

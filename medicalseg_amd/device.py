@@ -200,6 +200,11 @@ class ActivationArena:
                                "forward to backward would be zeroed under their readers (enlarge kRing in msk_scalar_slots)"
                                % (used, self.RING_HALF))
 
+    def restart_ring_count(self):
+        """Forget the amax requests counted so far: the next reset() measures from its own reading.  For callers that take amax
+        arrays outside a training step (direct use of Device.amax_new), whose requests are no step's."""
+        self._ring_served = None
+
     def alloc(self, nbytes: int) -> int:
         nbytes = (int(nbytes) + 255) & ~255
         while True:
