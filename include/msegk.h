@@ -721,7 +721,7 @@ int msk_boundary_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels
  *      CTNormalization, ZScoreNormalization; preprocess.fg_stats_device / clip_zscore_device / nonzero_bbox_device;
  *      tests/normalize_reference.py is the statement) ---- */
 #define MSK_MASK_ALL 0      /* every voxel is valid */
-#define MSK_MASK_NONZERO 1  /* x != 0 (so -0.0 is outside): nnU-Net's non-zero mask without its hole filling */
+#define MSK_MASK_NONZERO 1  /* x != 0 (so -0.0 is outside); nnU-Net's hole-filled mask: msk_fill_holes3d, then MSK_MASK_LABEL */
 #define MSK_MASK_LABEL 2    /* mask > 0, mask an int32 buffer of n words */
 #define MSK_NORM_CLIP 1     /* flags of msk_clip_zscore */
 #define MSK_NORM_ZSCORE 2
@@ -883,6 +883,31 @@ int msk_label_remap(msk_ctx* ctx, int32_t* label, size_t count, const int32_t* k
 int msk_connected_components3d(msk_ctx* ctx, const void* src, int32_t* dst, int n, int d, int h,
                                int w, int dtype, int minimum_volume, int k, int32_t* status,
                                int32_t* counts);
+/* Hole filling: scipy.ndimage.binary_fill_holes (nnU-Net's create_nonzero_mask) and MONAI's FillHoles on n independent
+ * contiguous d*h*w volumes; tests/fillholes_reference.py is the statement.  A voxel is zero when its value == 0 (float32: -0.0 is
+ * zero, a NaN is not: msk_nonzero_bbox's rule).  The zero voxels form 6-connected components; a component is a HOLE when none
+ * of its voxels lies on a face of the volume (an axis of extent 1 or 2 admits none).
+ *   MSK_FILL_MASK   dst = 1 where src != 0 or the voxel lies in a hole, else 0 (dtype 0 = float32 or 1 = int32);
+ *   MSK_FILL_LABEL  (dtype 1 only) dst = src, except that a hole whose non-zero 6-neighbours all carry ONE value c -- and,
+ *                   with nclasses > 0, c is one of classes -- becomes c; a hole between two or more values stays 0.
+ * dst (int32) may be src itself for dtype 1 (the last pass is elementwise and runs behind the last neighbour read); any other
+ * overlap is an error.  classes: a HOST array of at most 64 values, read before the call returns; nclasses == 0 = any value;
+ * only MSK_FILL_LABEL takes any.  status[n] (device, required): bit 1 = an internal iteration bound was hit
+ * (msk_connected_components3d's bit; bit 0 is never set: there is no binary check).  counts[n] (device, may be NULL): the
+ * number of voxels changed per volume.  Five launches on the context stream: the status / count words, msk_connected_components3d's
+ * tile-local and face-merge union-find on the zero voxels, a pass that sends every root to its voxels and gathers per root
+ * {touches a face, smallest, largest enclosing value} (merged per tile in LDS, integer atomics gated by an agent-scope load),
+ * the elementwise apply with one count atomic per workgroup and volume.  Integer atomics only: the result does not depend on
+ * the schedule.  Asynchronous: the caller reads status after synchronising.  n*d*h*w < 2^30; scratch from the context
+ * workspace: 2 int32 words per voxel for MSK_FILL_MASK (link, flag), 4 for MSK_FILL_LABEL (link, flag, smallest, largest).
+ * Argument errors, reported before any launch: an unknown dtype or mode, float32 with MSK_FILL_LABEL, an extent < 1, 2^30
+ * voxels or more, a null src / dst / status, nclasses outside [0, 64] or without classes or without MSK_FILL_LABEL, dst
+ * overlapping src other than dst == src for int32.                                                                          */
+#define MSK_FILL_MASK 0
+#define MSK_FILL_LABEL 1
+#define MSK_FILL_NONE 2 /* dst = (src != 0) for either dtype: the apply pass alone, nothing is searched or filled, counts = 0 */
+int msk_fill_holes3d(msk_ctx* ctx, const void* src, int32_t* dst, int n, int d, int h, int w, int dtype, int mode,
+                     const int32_t* classes, int nclasses, int32_t* status, int32_t* counts);
 /* utils/metric.py:21-61 calculate_area, as the confusion counts every hard-label metric (mean_iou, dice, accuracy,
  * kappa: metric.py:110-210) is a sum of.  pred / label: n contiguous volumes of voxels_per_volume int32 values
  * (4-byte alignment is enough).  counts (device): n rows of K*K + 1 unsigned 64-bit words, K = num_classes + 1:

@@ -186,6 +186,7 @@ SIGNATURES = {
     "msk_max_norm": (_i, [_vp, _vp, _vp, _sz]),
     "msk_label_remap": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     "msk_connected_components3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "msk_fill_holes3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "msk_confusion3d": (_i, [_vp, _vp, _vp, _i, C.c_long, _i, _i, _vp, _i]),
     "msk_auc_pack": (_i, [_vp, _T, _vp, _vp, C.c_long, C.c_long, _vp]),
     "msk_auc_workspace": (_i, [C.c_long, _i, C.POINTER(_sz)]),

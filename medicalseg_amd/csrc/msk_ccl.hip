@@ -25,6 +25,9 @@
 // Status word per volume (caller-owned, written by the device; no host synchronisation inside the call):
 //   bit 0 -- the volume holds 3 or more distinct values (the reference's binary assert);
 //   bit 1 -- a find / union loop hit its iteration bound (a bug, not an input property: the labels are garbage).
+//
+// msk_fill_holes3d (at the end of the file) runs the local and merge passes on the ZERO voxels instead, with the links in
+// scratch, and follows them with a gather of three words per root and an elementwise apply: no compaction, sort or rank.
 #include <algorithm>
 #include <climits>
 #include <type_traits>
@@ -68,8 +71,10 @@ __device__ __forceinline__ int order_key(T v) {
 
 __global__ void ccl_init_k(int* __restrict__ mm, int* __restrict__ status, int* __restrict__ counts, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    mm[2 * i] = INT_MAX;
-    mm[2 * i + 1] = INT_MIN;
+    if (mm) {   // hole filling has no binary check
+      mm[2 * i] = INT_MAX;
+      mm[2 * i + 1] = INT_MIN;
+    }
     status[i] = 0;
     if (counts) counts[i] = 0;
   }
@@ -114,7 +119,11 @@ __device__ __forceinline__ void lds_union(int* lp, int a, int b, bool& bad) {
   bad = true;
 }
 
-template <typename T>
+// FILL == 0: the members are the voxels != 0 and sizes[] is cleared (connected components).  FILL == 1 | 3 (hole filling):
+// the members are the voxels == 0 (-0.0 is one, a NaN is not), `sizes` holds FILL words per voxel that are initialised at
+// the tile-local roots only -- {border flag = 0}, then {smallest, largest enclosing value} = {INT_MAX, INT_MIN} -- and mm is
+// not used.
+template <typename T, int FILL>
 __global__ void __launch_bounds__(kThreads)
 ccl_local_k(const T* __restrict__ src, int* __restrict__ par, int* __restrict__ sizes, int* __restrict__ mm,
             int* __restrict__ status, Geo g) {
@@ -135,7 +144,7 @@ ccl_local_k(const T* __restrict__ src, int* __restrict__ par, int* __restrict__ 
       const int key = order_key(s);
       lo = min(lo, key);
       hi = max(hi, key);
-      if (s != (T)0) v = l;
+      if (FILL ? s == (T)0 : s != (T)0) v = l;
     }
     lp[l] = v;
   }
@@ -171,11 +180,19 @@ ccl_local_k(const T* __restrict__ src, int* __restrict__ par, int* __restrict__ 
         out = (int)(vbase + ((size_t)(z0 + rz) * g.h + (y0 + ry)) * g.w + (x0 + rx));
       }
       par[gi] = out;
-      sizes[gi] = 0;
+      if constexpr (FILL == 0) {
+        sizes[gi] = 0;
+      } else if (out == (int)gi) {   // a root of the merged forest is a root here: the words of the others are never read
+        sizes[FILL * gi] = 0;
+        if constexpr (FILL == 3) {
+          sizes[3 * gi + 1] = INT_MAX;
+          sizes[3 * gi + 2] = INT_MIN;
+        }
+      }
     }
   }
   if (bad) atomicOr(&status[vol], kStatusBound);
-  if (tid == 0) {
+  if (FILL == 0 && tid == 0) {
     for (int w = 1; w < kThreads / 64; ++w) {   // lane 0 of wavefront 0 already holds its own wavefront's
       lo = min(lo, smin[w]);
       hi = max(hi, smax[w]);
@@ -537,7 +554,7 @@ int run_ccl(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w
   }
   {
     msk_launch_scope ls(ctx, "ccl_local");
-    hipLaunchKernelGGL(ccl_local_k<T>, dim3((unsigned)ntiles), dim3(kThreads), 0, st, src, par, sizes, mm, status, g);
+    hipLaunchKernelGGL((ccl_local_k<T, 0>), dim3((unsigned)ntiles), dim3(kThreads), 0, st, src, par, sizes, mm, status, g);
     MSK_LAUNCH_CHECK(ctx);
   }
   {
@@ -595,6 +612,283 @@ int run_ccl(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w
   return 0;
 }
 
+// ---- hole filling ---------------------------------------------------------------------------------------------------
+// The components of the ZERO voxels (ccl_local_k<T, FILL>, ccl_merge_k), then per root the words {touches a face of the
+// volume (OR)} and, for the label form, {smallest, largest non-zero 6-neighbour (MIN, MAX)}; a hole is a component whose
+// flag stayed 0, and the label form fills it when smallest == largest.  None of compaction, sort, rank and relabel.
+constexpr int kFillMaxClasses = 64;
+struct FillClasses {
+  int n;
+  int v[kFillMaxClasses];
+};
+
+// gather (a new launch: the links are final): every zero voxel -> its root, as in ccl_flatten_k; what the voxel brings to
+// its root's words is merged per tile in an LDS hash, so a tile sends at most one atomic per (root, word), and only where
+// an agent-scope load says the word still moves -- the outside component is present in almost every tile, and after the
+// first few tiles nothing more is sent for it.  A stale load can only cost an atomic that was not needed (the flag only
+// rises, the minimum only falls, the maximum only rises).  A voxel that brings nothing (interior of a zero region) skips
+// the hash.
+// A tile of 1024 voxels holds at most 512 6-connected pieces (the checkerboard), so 1024 slots keep the load factor <= 1/2;
+// five tables of that size are 20 KB, which leaves room for eight workgroups per CU.
+constexpr int kFillHash = kTile;
+template <typename T, bool LABEL>
+__global__ void __launch_bounds__(kThreads)
+fill_gather_k(const T* __restrict__ src, int* __restrict__ par, int* __restrict__ words, int* __restrict__ status, Geo g) {
+  constexpr int W = LABEL ? 3 : 1;
+  __shared__ int hkey[kFillHash], hflag[kFillHash];
+  __shared__ int hlo[LABEL ? kFillHash : 1], hhi[LABEL ? kFillHash : 1], hshared[LABEL ? kFillHash : 1];
+  for (int i = threadIdx.x; i < kFillHash; i += kThreads) {
+    hkey[i] = -1;
+    hflag[i] = 0;
+    if constexpr (LABEL) {
+      hlo[i] = INT_MAX;
+      hhi[i] = INT_MIN;
+      hshared[i] = 0;
+    }
+  }
+  __syncthreads();
+  int vol, z0, y0, x0;
+  tile_coords(g, blockIdx.x, vol, z0, y0, x0);
+  const size_t vbase = (size_t)vol * g.vv;
+  const long hw = (long)g.h * g.w;
+  const int tid = threadIdx.x, y = tid / kTW, x = tid % kTW;
+  const int lane = tid % 64;
+  bool bad = false;
+  // what one lane sends to the hash for root `key`
+  auto insert = [&](int key, bool flag, int lo, int hi, bool crosses) {
+    unsigned s = ((unsigned)key * 2654435761u) % kFillHash;
+    for (int probe = 0; probe < kFillHash; ++probe) {   // at most kTile / 2 distinct keys in kTile slots
+      const int k = atomicCAS(&hkey[s], -1, key);
+      if (k == -1 || k == key) {
+        if (flag) atomicOr(&hflag[s], 1);
+        if constexpr (LABEL) {
+          if (lo <= hi) {
+            atomicMin(&hlo[s], lo);
+            atomicMax(&hhi[s], hi);
+          }
+          if (crosses) atomicOr(&hshared[s], 1);
+        }
+        return;
+      }
+      s = s + 1 == kFillHash ? 0 : s + 1;
+    }
+  };
+  // label form: the thread's four values stay in registers -- its z-neighbours are its own, its x-neighbours and one of its
+  // y-neighbours are other lanes' of the wavefront (two rows of 32), the rest (tile faces) comes from memory
+  int v[kTD];
+  if constexpr (LABEL) {
+#pragma unroll
+    for (int z = 0; z < kTD; ++z) {
+      const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+      v[z] = gz < g.d && gy < g.h && gx < g.w ? (int)src[vbase + ((size_t)gz * g.h + gy) * g.w + gx] : 1;
+    }
+  }
+#pragma unroll
+  for (int z = 0; z < kTD; ++z) {
+    const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+    const bool inside = gz < g.d && gy < g.h && gx < g.w;
+    const size_t gi = vbase + ((size_t)gz * g.h + gy) * g.w + gx;   // dereferenced only when inside
+    int a = inside ? par[gi] : -1;
+    const bool member = a >= 0;
+    bool border = false;
+    if (member) {
+      int p = par[a];
+      for (long it = 0; p != a; ++it) {
+        if (it > g.vv) { bad = true; break; }
+        a = p;
+        p = par[a];
+      }
+      par[gi] = a;
+      border = gz == 0 || gy == 0 || gx == 0 || gz == g.d - 1 || gy == g.h - 1 || gx == g.w - 1;
+    }
+    int lo = INT_MAX, hi = INT_MIN;
+    bool crosses = false;   // a zero neighbour in another tile: the component is not this tile's alone
+    if constexpr (LABEL) {
+      const int left = __shfl_up(v[z], 1, 64), right = __shfl_down(v[z], 1, 64);
+      const int up = __shfl_up(v[z], kTW, 64), down = __shfl_down(v[z], kTW, 64);
+      if (member) {
+        auto see = [&](int nv) {
+          if (nv != 0) {
+            lo = min(lo, nv);
+            hi = max(hi, nv);
+          }
+        };
+        auto across = [&](size_t j, bool other_tile) {
+          const int nv = (int)src[j];
+          crosses |= other_tile && nv == 0;
+          return nv;
+        };
+        if (gx > 0) see(x > 0 ? left : across(gi - 1, true));
+        if (gx < g.w - 1) see(x < kTW - 1 ? right : across(gi + 1, true));
+        if (gy > 0) see(lane >= kTW ? up : across(gi - g.w, y == 0));
+        if (gy < g.h - 1) see(lane < kTW ? down : across(gi + g.w, y == kTH - 1));
+        if (gz > 0) see(z > 0 ? v[z > 0 ? z - 1 : 0] : across(gi - hw, true));
+        if (gz < g.d - 1) see(z < kTD - 1 ? v[z < kTD - 1 ? z + 1 : z] : across(gi + hw, true));
+      }
+    }
+    // Lanes of one wavefront that bring something to the same root merge in registers first: a region's voxels all hit ONE
+    // hash slot, and LDS atomics on one address serialise.  Up to four roots per wavefront and z (the leader's of the lanes
+    // still waiting, a group of one goes straight in); whatever waits after that goes in lane by lane.
+    bool has = member && (border || lo <= hi || crosses);
+    unsigned long long todo = __ballot(has);
+    for (int round = 0; round < 4 && todo; ++round) {   // wave-uniform
+      const int leader = __ffsll(todo) - 1;
+      const int key = __shfl(a, leader, 64);
+      const bool mine = has && a == key;
+      const unsigned long long grp = __ballot(mine);
+      if (__popcll(grp) > 1) {
+        const bool f = __ballot(mine && border) != 0, cr = __ballot(mine && crosses) != 0;
+        int l = mine ? lo : INT_MAX, hh = mine ? hi : INT_MIN;
+        if constexpr (LABEL) {
+          for (int o = 32; o > 0; o >>= 1) {
+            l = min(l, __shfl_xor(l, o, 64));
+            hh = max(hh, __shfl_xor(hh, o, 64));
+          }
+        }
+        if (lane == leader) insert(key, f, l, hh, cr);
+      } else if (lane == leader) {
+        insert(a, border, lo, hi, crosses);
+      }
+      has = has && !mine;
+      todo &= ~grp;
+    }
+    if (has) insert(a, border, lo, hi, crosses);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kFillHash; i += kThreads) {
+    const int k = hkey[i];
+    if (k < 0) continue;
+    int* wk = words + (size_t)W * k;
+    if constexpr (LABEL) {
+      // no voxel of the component has a zero neighbour across a tile face: all of it, its root included, lies in this tile
+      // and nobody else sends anything for it -- plain stores.  (The many small holes of a prediction; an atomic on a word
+      // of its own costs a trip to memory each.)
+      if (!hshared[i]) {
+        wk[0] = hflag[i];
+        wk[1] = hlo[i];
+        wk[2] = hhi[i];
+        continue;
+      }
+    }
+    if (hflag[i] && !ld_agent(&wk[0])) atomicOr(&wk[0], 1);
+    if constexpr (LABEL) {
+      if (hlo[i] < ld_agent(&wk[1])) atomicMin(&wk[1], hlo[i]);
+      if (hhi[i] > ld_agent(&wk[2])) atomicMax(&wk[2], hhi[i]);
+    }
+  }
+  if (bad) atomicOr(&status[vol], kStatusBound);
+}
+
+// apply (a new launch: the words are final, and no neighbour is read any more, so dst may be src): one streaming pass;
+// blockIdx.y walks the volumes, so a workgroup's count of filled voxels belongs to one volume at a time -- registers, a
+// wavefront reduction, LDS, then one atomic per workgroup and volume.
+template <typename T, bool LABEL>
+__global__ void __launch_bounds__(kThreads)
+fill_apply_k(const T* src, int* dst, const int* __restrict__ par, const int* __restrict__ words, int* __restrict__ counts,
+             long vv, int n, FillClasses cls) {
+  __shared__ int wsum[kThreads / 64];
+  const int tid = threadIdx.x;
+  for (int vol = blockIdx.y; vol < n; vol += gridDim.y) {
+    const size_t vbase = (size_t)vol * vv;
+    int cnt = 0;
+    for (long r = (long)blockIdx.x * kThreads + tid; r < vv; r += (long)gridDim.x * kThreads) {
+      const size_t i = vbase + r;
+      const T s = src[i];
+      int out;
+      if (s != (T)0) {
+        out = LABEL ? (int)s : 1;
+      } else {
+        const int root = par ? par[i] : 0;
+        bool fill;
+        int c = 1;
+        if constexpr (LABEL) {
+          const int* wk = words + 3 * (size_t)root;
+          fill = wk[0] == 0;
+          if (fill) {
+            c = wk[1];
+            fill = c == wk[2];
+          }
+          if (fill && cls.n > 0) {
+            bool in = false;
+            for (int j = 0; j < cls.n; ++j) in |= cls.v[j] == c;
+            fill = in;
+          }
+        } else {
+          fill = words && words[root] == 0;   // words == nullptr (uniform): MSK_FILL_NONE, nothing is filled
+        }
+        out = fill ? c : 0;
+        cnt += fill;
+      }
+      dst[i] = out;
+    }
+    if (counts) {   // uniform
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+      if (tid % 64 == 0) wsum[tid / 64] = cnt;
+      __syncthreads();
+      if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < kThreads / 64; ++w) total += wsum[w];
+        if (total) atomicAdd(&counts[vol], total);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+template <typename T, bool LABEL>
+int run_fill(msk_ctx* ctx, const T* src, int32_t* dst, int n, int d, int h, int w, const FillClasses& cls, bool search,
+             int32_t* status, int32_t* counts) {
+  constexpr int W = LABEL ? 3 : 1;
+  Geo g;
+  g.d = d;
+  g.h = h;
+  g.w = w;
+  g.tz = (d + kTD - 1) / kTD;
+  g.ty = (h + kTH - 1) / kTH;
+  g.tx = (w + kTW - 1) / kTW;
+  g.vv = (long)d * h * w;
+  const long T_ = (long)n * g.vv;
+  int* par = nullptr;
+  int* words = nullptr;
+  if (search) {
+    par = (int*)msk_workspace(ctx, (size_t)(1 + W) * T_ * sizeof(int));   // dst may be src: the links live in scratch
+    if (!par) return -1;
+    words = par + T_;
+  }
+  const long ntiles = (long)n * g.tz * g.ty * g.tx;
+  hipStream_t st = ctx->stream;
+  {
+    msk_launch_scope ls(ctx, "fill_init");
+    hipLaunchKernelGGL(ccl_init_k, dim3(std::max(1, std::min(64, (n + kThreads - 1) / kThreads))), dim3(kThreads), 0, st,
+                       (int*)nullptr, status, counts, n);
+    MSK_LAUNCH_CHECK(ctx);
+  }
+  if (search) {
+    msk_launch_scope ls(ctx, "fill_local");
+    hipLaunchKernelGGL((ccl_local_k<T, W>), dim3((unsigned)ntiles), dim3(kThreads), 0, st, src, par, words, (int*)nullptr,
+                       status, g);
+    MSK_LAUNCH_CHECK(ctx);
+  }
+  if (search) {
+    msk_launch_scope ls(ctx, "fill_merge");
+    hipLaunchKernelGGL(ccl_merge_k, dim3(msk_ew_blocks(T_, ctx->num_cu)), dim3(kThreads), 0, st, par, status, g, T_);
+    MSK_LAUNCH_CHECK(ctx);
+  }
+  if (search) {
+    msk_launch_scope ls(ctx, "fill_gather");
+    hipLaunchKernelGGL((fill_gather_k<T, LABEL>), dim3((unsigned)ntiles), dim3(kThreads), 0, st, src, par, words, status, g);
+    MSK_LAUNCH_CHECK(ctx);
+  }
+  {
+    msk_launch_scope ls(ctx, "fill_apply");
+    const unsigned bx = (unsigned)std::max(1, msk_ew_blocks(g.vv, ctx->num_cu) / std::min(n, 8));
+    hipLaunchKernelGGL((fill_apply_k<T, LABEL>), dim3(bx, (unsigned)std::min(n, 65535)), dim3(kThreads), 0, st, src, dst,
+                       (const int*)par, (const int*)words, counts, g.vv, n, cls);
+    MSK_LAUNCH_CHECK(ctx);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -608,6 +902,32 @@ int msk_connected_components3d(msk_ctx* ctx, const void* src, int32_t* dst, int 
   MSK_REQUIRE(ctx, src != (const void*)dst, "connected components are out of place");
   if (dtype == 0) return run_ccl(ctx, (const float*)src, dst, n, d, h, w, minimum_volume, k, status, counts);
   return run_ccl(ctx, (const int32_t*)src, dst, n, d, h, w, minimum_volume, k, status, counts);
+}
+
+int msk_fill_holes3d(msk_ctx* ctx, const void* src, int32_t* dst, int n, int d, int h, int w, int dtype, int mode,
+                     const int32_t* classes, int nclasses, int32_t* status, int32_t* counts) {
+  MSK_REQUIRE(ctx, dtype == 0 || dtype == 1, "dtype must be 0 (float32) or 1 (int32)");
+  MSK_REQUIRE(ctx, mode == MSK_FILL_MASK || mode == MSK_FILL_LABEL || mode == MSK_FILL_NONE,
+              "mode must be MSK_FILL_MASK, MSK_FILL_LABEL or MSK_FILL_NONE");
+  MSK_REQUIRE(ctx, dtype == 1 || mode != MSK_FILL_LABEL, "a float32 volume has no label form");
+  MSK_REQUIRE(ctx, n > 0 && d > 0 && h > 0 && w > 0, "empty volume");
+  MSK_REQUIRE(ctx, (long)n * d * h * w <= (long)INT_MAX / 2, "n*d*h*w must stay below 2^30 (int32 voxel indices)");
+  MSK_REQUIRE(ctx, src && dst && status, "src, dst and status are required");
+  MSK_REQUIRE(ctx, nclasses >= 0 && nclasses <= kFillMaxClasses, "at most 64 classes");
+  MSK_REQUIRE(ctx, nclasses == 0 || classes, "classes is null");
+  MSK_REQUIRE(ctx, nclasses == 0 || mode == MSK_FILL_LABEL, "only MSK_FILL_LABEL takes classes");
+  const size_t bytes = (size_t)n * d * h * w * 4;
+  const char *sb = (const char*)src, *db = (const char*)dst;
+  MSK_REQUIRE(ctx, (sb == db && dtype == 1) || sb + bytes <= db || db + bytes <= sb,
+              "dst may be src itself (int32 only) and must not overlap it otherwise");
+  FillClasses cls;
+  cls.n = nclasses;
+  for (int i = 0; i < kFillMaxClasses; ++i) cls.v[i] = i < nclasses ? classes[i] : 0;
+  const bool search = mode != MSK_FILL_NONE;
+  if (dtype == 0) return run_fill<float, false>(ctx, (const float*)src, dst, n, d, h, w, cls, search, status, counts);
+  if (mode != MSK_FILL_LABEL)
+    return run_fill<int32_t, false>(ctx, (const int32_t*)src, dst, n, d, h, w, cls, search, status, counts);
+  return run_fill<int32_t, true>(ctx, (const int32_t*)src, dst, n, d, h, w, cls, true, status, counts);
 }
 
 }  // extern "C"

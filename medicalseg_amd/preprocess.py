@@ -209,6 +209,160 @@ def connected_components_device(x, minimum_volume=0, k=0):
     return out
 
 
+# ---- hole filling (scipy.ndimage.binary_fill_holes = nnU-Net's create_nonzero_mask; MONAI's FillHoles) -------------------------
+FILL_MASK, FILL_LABEL, FILL_NONE = 0, 1, 2       # MSK_FILL_*
+FILL_MAX_CLASSES = 64
+
+
+def _fill_classes(classes, binary):
+    """the ``classes`` argument as an int32 array (empty: any value)"""
+    cls = np.zeros(0, np.int32) if classes is None else np.atleast_1d(np.asarray(classes)).astype(np.int32).reshape(-1)
+    if cls.size > FILL_MAX_CLASSES:
+        raise ValueError("at most {} classes, got {}".format(FILL_MAX_CLASSES, cls.size))
+    if binary and cls.size:
+        raise ValueError("binary=True fills every hole of the non-zero mask and takes no classes")
+    return cls
+
+
+def fill_holes_device(x, classes=None, binary=False):
+    """msk_fill_holes3d: the enclosed holes of every volume filled on the device (tests/fillholes_reference.py is the statement).
+    The zero voxels (value == 0; float32: -0.0 is zero, a NaN is not) form 6-connected components; one that touches no face of
+    the volume is a hole.  ``binary=True``: the int32 mask 1 where x != 0 or in a hole, else 0 -- exactly
+    scipy.ndimage.binary_fill_holes(x != 0).  ``binary=False`` (int32 only, MONAI's FillHoles): x with every hole whose non-zero
+    6-neighbours all carry ONE value c set to c, when c is in ``classes`` (None: any value; at most 64); a hole between
+    different values stays 0.
+
+    x: a 3-D float32 (``binary=True`` only) / int32 ``DeviceVolume`` -> a new pooled int32 ``DeviceVolume``; or an
+    ``IntTensor`` [N, 1, D, H, W] -> a new ``IntTensor`` in the activation arena (valid until the next model forward), each of
+    the N volumes on its own.  The input is not modified.  Synchronises once, to read the per-volume status words (4 bytes
+    each): an iteration bound that was hit raises MskError."""
+    from .device import IntTensor
+    cls = _fill_classes(classes, binary)
+    if isinstance(x, DeviceVolume):
+        if len(x.shape) != 3:
+            raise ValueError("expected a 3-D volume, got shape {}".format(x.shape))
+        if x.dtype not in (np.float32, np.int32):
+            raise TypeError("fill_holes_device takes a float32 or int32 volume, got {}".format(x.dtype))
+        if x.dtype == np.float32 and not binary:
+            raise ValueError("a float32 volume has no label form: pass binary=True for the filled non-zero mask")
+        n, (d, h, w), dtype = 1, x.shape, _dt(x)
+        out = _pooled_volume(x.dev, x.shape, np.int32)
+    elif isinstance(x, IntTensor):
+        if len(x.shape) != 5 or x.shape[1] != 1:
+            raise ValueError("expected an [N, 1, D, H, W] label tensor, got shape {}".format(x.shape))
+        n, _, d, h, w = x.shape
+        dtype = 1
+        out = IntTensor(x.dev, x.dev.arena.alloc(int(np.prod(x.shape)) * 4), x.shape, x.dev.arena.gen)
+    else:
+        raise TypeError("fill_holes_device takes a DeviceVolume or an IntTensor, got {}".format(type(x)))
+    dev = x.dev
+    try:
+        with _pooled_scratch(dev, 4 * n) as st:
+            dev.call("msk_fill_holes3d", C.c_void_p(x.ptr), C.c_void_p(out.ptr), n, d, h, w, dtype,
+                     FILL_MASK if binary else FILL_LABEL, cls.ctypes.data_as(C.c_void_p) if cls.size else None, int(cls.size),
+                     C.c_void_p(st), None)
+            status = dev.d2h(st, (n,), np.int32)
+        if status.any():
+            raise MskError("msk_fill_holes3d: an iteration bound was hit (status {})".format(status.tolist()))
+    except BaseException:
+        if isinstance(out, DeviceVolume):
+            out.free()
+        raise
+    return out
+
+
+def _fill_holes_volume(x, cls, binary):
+    """one 3-D host volume -> int32, the statement of tests/fillholes_reference.py vectorised over the components"""
+    import scipy.ndimage
+    zero = x == 0
+    lab, n = scipy.ndimage.label(zero)
+    hole = np.ones(n + 1, bool)
+    hole[0] = False                                    # entry 0: the non-zero voxels
+    for ax in range(3):
+        for face in (0, -1):
+            hole[np.take(lab, face, axis=ax).ravel()] = False
+    if binary:
+        return (~zero | hole[lab]).astype(np.int32)
+    lo = np.full(n + 1, np.iinfo(np.int64).max, np.int64)
+    hi = np.full(n + 1, np.iinfo(np.int64).min, np.int64)
+    for ax in range(3):
+        a, b = [slice(None)] * 3, [slice(None)] * 3
+        a[ax], b[ax] = slice(0, -1), slice(1, None)
+        for p, q in ((tuple(a), tuple(b)), (tuple(b), tuple(a))):   # p: the zero voxel, q: its neighbour along the axis
+            sel = zero[p] & ~zero[q]
+            np.minimum.at(lo, lab[p][sel], x[q][sel].astype(np.int64))
+            np.maximum.at(hi, lab[p][sel], x[q][sel].astype(np.int64))
+    ok = hole & (lo == hi)
+    if cls.size:
+        ok &= np.isin(lo, cls.astype(np.int64))
+    return np.where(ok[lab], lo[lab], x.astype(np.int64)).astype(np.int32)
+
+
+def fill_holes_host(x, classes=None, binary=False) -> np.ndarray:
+    """fill_holes_device in numpy and scipy.ndimage.label, the same values: a [D, H, W] volume or a batch [N, 1, D, H, W],
+    every volume on its own -> int32 of the same shape"""
+    cls = _fill_classes(classes, binary)
+    x = np.asarray(x)
+    if x.ndim == 5 and x.shape[1] == 1:
+        if not x.shape[0]:
+            raise ValueError("empty batch")
+        return np.stack([fill_holes_host(v[0], classes, binary)[None] for v in x])
+    if x.ndim != 3:
+        raise ValueError("expected a 3-D volume or an [N, 1, D, H, W] batch, got shape {}".format(x.shape))
+    if not binary and not np.issubdtype(x.dtype, np.integer):
+        raise ValueError("a float32 volume has no label form: pass binary=True for the filled non-zero mask")
+    return _fill_holes_volume(x, cls, binary)
+
+
+def fill_holes(x, classes=None, binary=False, on_device=True) -> np.ndarray:
+    """fill_holes_device for a host array [D, H, W] (uploaded, filled, downloaded) -> int32; ``on_device`` False takes
+    fill_holes_host, which gives the same values"""
+    if not on_device:
+        return fill_holes_host(x, classes, binary)
+    _fill_classes(classes, binary)
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError("expected a 3-D volume, got shape {}".format(x.shape))
+    if np.issubdtype(x.dtype, np.integer):
+        vol = upload(x.astype(np.int32))
+    elif binary:
+        vol = upload(x.astype(np.float32))
+    else:
+        raise ValueError("a float32 volume has no label form: pass binary=True for the filled non-zero mask")
+    try:
+        out = fill_holes_device(vol, classes, binary)
+    finally:
+        vol.free()
+    res = out.numpy()
+    out.free()
+    return res
+
+
+def nonzero_mask_device(vol: DeviceVolume, fill_holes=True) -> DeviceVolume:
+    """nnU-Net's create_nonzero_mask, binary_fill_holes(x != 0), as a new pooled int32 volume of 0 / 1 ready for mode='mask'
+    (``fill_holes`` False: x != 0 alone).  Downloads the 4-byte status word of fill_holes_device.  One channel: nnU-Net ORs the
+    mask over the modalities of a case."""
+    if not isinstance(vol, DeviceVolume) or len(vol.shape) != 3:
+        raise TypeError("nonzero_mask_device takes a 3-D DeviceVolume")
+    if fill_holes:
+        return fill_holes_device(vol, binary=True)
+    if vol.dtype not in (np.float32, np.int32):
+        raise TypeError("nonzero_mask_device takes a float32 or int32 volume, got {}".format(vol.dtype))
+    with _pooled_outputs(vol.dev, (vol.shape, np.int32)) as (out,), _pooled_scratch(vol.dev, 4) as st:
+        # MSK_FILL_NONE is the apply pass alone: no search, so no bound can be hit and the status word is not read
+        vol.dev.call("msk_fill_holes3d", C.c_void_p(vol.ptr), C.c_void_p(out.ptr), 1, *vol.shape, _dt(vol), FILL_NONE, None, 0,
+                     C.c_void_p(st), None)
+    return out
+
+
+def nonzero_mask_host(volume, fill_holes=True) -> np.ndarray:
+    """nonzero_mask_device in numpy: int32 0 / 1"""
+    v = np.asarray(volume)
+    if v.ndim != 3:
+        raise ValueError("expected a 3-D volume, got shape {}".format(v.shape))
+    return fill_holes_host(v, binary=True) if fill_holes else (v != 0).astype(np.int32)
+
+
 def patch_select_device(label: DeviceVolume, roi, num_classes, classes, words) -> DeviceVolume:
     """msk_patch_select: choose patch origins in a device label volume -> the ``sel`` records, an int32 ``DeviceVolume``
     [n_patches, 8] (d0, h0, w0, cls, cz, cy, cx, 0) from the stream-ordered pool (``free()`` hands it back).
@@ -418,8 +572,8 @@ def crop_to_nonzero_device(img: DeviceVolume, label=None):
 
 
 def fg_stats_device(vol: DeviceVolume, mask=None, mode="all", percentiles=(0.5, 99.5)) -> DeviceVolume:
-    """msk_fg_stats: the record FG_FIELDS of the valid voxels of a float32 volume (``mode`` 'all'; 'nonzero': x != 0, nnU-Net's
-    non-zero mask without its hole filling; 'mask': ``mask`` > 0, an int32 volume) as sixteen float64 in a pooled device buffer:
+    """msk_fg_stats: the record FG_FIELDS of the valid voxels of a float32 volume (``mode`` 'all'; 'nonzero': x != 0;
+    'mask': ``mask`` > 0, an int32 volume -- nonzero_mask_device gives nnU-Net's hole-filled non-zero mask) as sixteen float64 in a pooled device buffer:
     count, exact min / max, the float64 sums in msk_intensity_stats' fixed order, mean, std and the two ``percentiles`` by
     numpy's default method, every field exact (tests/normalize_reference.py).  The workspace comes from the pool and goes back
     to it.  Nothing is downloaded and nothing synchronises: clip_zscore_device reads the record on the device."""
@@ -558,20 +712,37 @@ def ct_normalize(image, lo, hi, mean, std, on_device=True):
     return _on_host_array(lambda v: clip_zscore_device(v, lo=lo, hi=hi, mean=mean, std=std), image)
 
 
-def zscore_normalize(image, percentiles=None, mode="all", mask=None, on_device=True):
+def _check_fill_mode(fill_holes, mode):
+    if fill_holes and mode != "nonzero":
+        raise ValueError("fill_holes=True fills the holes of the non-zero mask and needs mode 'nonzero', got {!r}".format(mode))
+
+
+def zscore_normalize(image, percentiles=None, mode="all", mask=None, on_device=True, fill_holes=False):
     """nnU-Net's ZScoreNormalization per volume: mean and std of the valid voxels (``mode`` 'all', 'nonzero' or 'mask' with an
     integer ``mask``), after clipping to the two ``percentiles`` of the valid voxels when they are given (MONAI's
     ScaleIntensityRangePercentiles in front of NormalizeIntensity); with a mask the voxels outside it become 0.
+    ``mode='nonzero'`` alone is x != 0; with ``fill_holes=True`` (a [D, H, W] volume) it is nnU-Net's mask,
+    binary_fill_holes(x != 0): a zero voxel enclosed by the body is part of the statistics and is z-scored.  That is mode 'mask'
+    on nonzero_mask_device / nonzero_mask_host, whose device form downloads its 4-byte status word.
     ``on_device`` False takes the numpy host path, which gives the same bits."""
     _mask_mode(mode, mask)
+    _check_fill_mode(fill_holes, mode)
     q, clip, outside = _zscore_settings(percentiles, mode)
     _percentile_pair(q)
     if not on_device:
+        if fill_holes:
+            mask, mode = nonzero_mask_host(np.asarray(image, dtype=np.float32)), "mask"
         rec = fg_stats_host(image, mask, mode, q)
         return clip_zscore_host(image, stats=rec, mask=mask, mode=mode, clip=clip, outside=outside)
+    if fill_holes and np.ndim(image) != 3:
+        raise ValueError("expected a 3-D volume, got shape {}".format(np.shape(image)))
     vol = upload(np.asarray(image, dtype=np.float32))
-    mvol = upload(np.asarray(mask).astype(np.int32)) if mask is not None else None
+    mvol = None
     try:
+        if fill_holes:
+            mvol, mode = nonzero_mask_device(vol), "mask"
+        elif mask is not None:
+            mvol = upload(np.asarray(mask).astype(np.int32))
         rec = fg_stats_device(vol, mvol, mode, q)
         out = clip_zscore_device(vol, stats=rec, mask=mvol, mode=mode, clip=clip, outside=outside).numpy()
         rec.free()
@@ -851,17 +1022,27 @@ class _Chain:
         clip_zscore_device(self.vol, lo=lo, hi=hi, mean=mean, std=std)
         return self
 
-    def zscore(self, percentiles=None, mode="all"):
+    def zscore(self, percentiles=None, mode="all", fill_holes=False):
         """nnU-Net's ZScoreNormalization of this volume, in place: statistics of all voxels or of the non-zero ones (outside
-        them the result is 0), after clipping to the two ``percentiles`` when given; the record never leaves the device"""
+        them the result is 0), after clipping to the two ``percentiles`` when given; the record never leaves the device.
+        ``fill_holes=True`` with mode 'nonzero' normalises under nnU-Net's hole-filled mask (nonzero_mask_device: zero voxels
+        enclosed by the body are inside); that downloads the 4-byte status word of the hole filling, and the mask goes back to
+        the pool afterwards"""
         if mode not in ("all", "nonzero"):
             raise ValueError("a chain z-scores over 'all' or 'nonzero' voxels, got {!r}".format(mode))
+        _check_fill_mode(fill_holes, mode)
         q, clip, outside = _zscore_settings(percentiles, mode)
-        rec = fg_stats_device(self.vol, None, mode, q)
+        mask = nonzero_mask_device(self.vol) if fill_holes else None
+        mode = "mask" if fill_holes else mode
+        rec = None
         try:
-            clip_zscore_device(self.vol, stats=rec, mode=mode, clip=clip, outside=outside)
+            rec = fg_stats_device(self.vol, mask, mode, q)
+            clip_zscore_device(self.vol, stats=rec, mask=mask, mode=mode, clip=clip, outside=outside)
         finally:
-            rec.free()
+            if rec is not None:
+                rec.free()
+            if mask is not None:
+                mask.free()
         return self
 
     def tensor(self):

@@ -965,3 +965,32 @@ class TopkLargestConnectComponent:
         pred = _connected_components(pred)
         pred[pred > self.k] = 0
         return pred, label
+
+
+@manager.TRANSFORMS.add_component
+class FillHoles3D:
+    """MONAI's FillHoles for label volumes (not in the reference): a 6-connected region of zeros that touches no face of the
+    volume and whose non-zero neighbours all carry one value c becomes c, when c is in ``classes`` (None: any value; at most
+    64); a hole between different values stays 0.  On a binary mask this is scipy.ndimage.binary_fill_holes.  numpy volumes
+    [D, H, W] (or [N, 1, D, H, W]) take the host path (preprocess.fill_holes_host) and keep their dtype; a ``DeviceVolume`` or
+    an ``IntTensor`` [N, 1, D, H, W] takes the HIP path (preprocess.fill_holes_device, every volume on its own, one download
+    of the status words): int32 with the same values, on the device.  Composes with TopkLargestConnectComponent as a
+    ``pred_transform``."""
+
+    def __init__(self, classes=None):
+        from ..preprocess import _fill_classes
+        self.classes = None if classes is None else [int(c) for c in _fill_classes(classes, False)]
+
+    def _fill(self, vol):
+        from ..preprocess import fill_holes_device, fill_holes_host
+        if _cc_on_device(vol):
+            out = fill_holes_device(vol, self.classes)
+            return _swap(vol, out) if _on_device(vol) else out
+        vol = np.asarray(vol)
+        return fill_holes_host(vol, self.classes).astype(vol.dtype)
+
+    def __call__(self, pred, label=None):
+        pred = self._fill(pred)
+        if label is not None:
+            label = self._fill(label)
+        return pred, label
