@@ -645,6 +645,37 @@ int msk_region_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, 
                         int focal_on, float gamma, const float* weight, const double* stats, float coef_f, float coef_r,
                         int accumulate, msk_tensor dlogits);
 
+/* ---- region-based training: sigmoid Dice + BCE over label regions (DiceBCERegionLoss: nnU-Net's DC_and_BCE_loss and its
+ *      regions_class_order; tests/mlabel_reference.py is the statement) ---- */
+/* The R = logits.c channels (1 <= R <= 32) are overlapping REGIONS of the label map.  The label stays one int32 per voxel;
+ * table (DEVICE, table_len uint32, 1 <= table_len <= 256) maps a label value v to the bit mask of the regions it belongs to.
+ * Per voxel m = (label != ignore_index), t_r = bit r of table[label] when 0 <= label < table_len, otherwise 0 (a label outside
+ * the table that is not ignored gives an all-zero row), p_r = sigmoid(z_r) in the overflow-free form (exp(-|z|)).  Per group g
+ * (the batch when batch_dice != 0, else each sample; G groups) and region r: TP = sum m p t, SP = sum m p^q (q = 2 when
+ * squared_pred != 0, else 1), ST = sum m t.
+ *   score  = (2 TP + smooth) / den,  den = max(SP + ST + smooth, 1e-8)
+ *   L_dice = 1 - mean of score over the groups and ALL regions (there is no do_bg)
+ *   L_bce  = sum m sum_r (max(z, 0) - z t + log1p(exp(-|z|))) / (R sum m), 0 when no voxel is valid
+ *   dL/dz  = coef_bce m (p - t) / (R sum m) + coef_dice m (A t + B q p^(q-1)) p (1 - p)
+ *   A = -2 / (G R den),  B = (2 TP + smooth) / (G R den^2) where SP + ST + smooth > 1e-8, otherwise 0
+ * out (device, 2 + R floats) = {L_bce, L_dice, mean over the groups of score[., r] for every region r}.
+ * stats (device, 5 G R + 2 doubles) = TP[G][R], SP[G][R], ST[G][R], A[G][R], B[G][R], the BCE sum, sum m.
+ * Two launches; no float atomics, two calls give the same bits; nothing is downloaded and nothing synchronises.  With several
+ * ranks the sums are those of the calling rank. */
+int msk_mlabel_loss_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const uint32_t* table,
+                        int table_len, int squared_pred, int batch_dice, float smooth, float* out, double* stats);
+/* dlogits (+)= the gradient above from the stats of the forward call with the same settings (accumulate != 0 adds).  One
+ * launch.  Argument errors of both, reported before any launch: R outside 1..32, table_len outside 1..256, null or misaligned
+ * pointers, a dlogits of another shape or overlapping the logits, a voxel count at or above 2^31, smooth < 0. */
+int msk_mlabel_loss_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const uint32_t* table,
+                        int table_len, int squared_pred, int batch_dice, float smooth, const double* stats, float coef_bce,
+                        float coef_dice, int accumulate, msk_tensor dlogits);
+/* out [N,D,H,W] int32 = 0, then for r = 0 .. R-1 in order: out = class_order[r] where logit z_r > 0 (the last region that
+ * fires wins: nnU-Net's loop over regions_class_order; the comparison is on the logit, a NaN does not fire).  class_order: HOST,
+ * R = logits.c values, read during the call (it travels by value in the kernel arguments).  One launch; the same argument
+ * errors. */
+int msk_regions_to_label(msk_ctx* ctx, msk_tensor logits, const int32_t* class_order, int32_t* out);
+
 /* ---- top-k selection and top-k cross entropy (TopKLoss, DiceTopKLoss: nnU-Net's TopKLoss / DC_and_topk_loss;
  *      tests/topk_reference.py is the statement) ---- */
 /* Bytes of workspace for n values (in [1, 2^31)): the n floats of per-voxel loss, three 2048-bin histograms, 8 bytes per chunk of

@@ -155,6 +155,9 @@ SIGNATURES = {
     "msk_bce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _i, _T]),
     "msk_region_loss_fwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _vp]),
     "msk_region_loss_bwd": (_i, [_vp, _T, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _i, _T]),
+    "msk_mlabel_loss_fwd": (_i, [_vp, _T, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "msk_mlabel_loss_bwd": (_i, [_vp, _T, _vp, _i, _vp, _i, _i, _i, _f, _vp, _f, _f, _i, _T]),
+    "msk_regions_to_label": (_i, [_vp, _T, _vp, _vp]),
     "msk_topk_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
     "msk_topk_select": (_i, [_vp, _vp, C.c_long, C.c_long, _vp, _vp]),
     "msk_topk_ce_fwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _vp, _vp, _vp]),

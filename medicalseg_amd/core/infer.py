@@ -38,15 +38,19 @@ def reverse_transform(pred, ori_shape, transforms, mode='trilinear'):
     return pred
 
 
-def inference(model, im, ori_shape=None, transforms=None):
+def inference(model, im, ori_shape=None, transforms=None, regions=None):
     """Returns (pred int32 [N,1,D,H,W] on device, logits Tensor); with `ori_shape` different from the logits' and
     Resize3D ops in `transforms`, the logits are resized back first (infer.py:88-90).
+
+    regions (region-based training: a RegionSpec with class_order, e.g. DiceBCERegionLoss.region_spec): the channels are
+    sigmoid regions, and the prediction is rebuilt from the thresholded logits in the spec's order (msk_regions_to_label, after
+    the resize back) instead of the argmax.
 
     An eval-mode model runs its conv -> BN -> PReLU units as single folded convolutions here
     (nn.fused_inference); a model left in training mode runs the ordinary kernels."""
     with nn.fused_inference():
         logit = _forward(model, im)
-    return _finish(logit, ori_shape, transforms)
+    return _finish(logit, ori_shape, transforms, regions)
 
 
 # ---- what the three prediction paths (inference, aug_inference, sliding_window_inference) share ------------------------------
@@ -65,11 +69,13 @@ def _new_pred(logit):
     return IntTensor(dev, dev.arena.alloc(logit.voxels * 4), (logit.n, 1, logit.d, logit.h, logit.w), dev.arena.gen)
 
 
-def _finish(logit, ori_shape, transforms):
+def _finish(logit, ori_shape, transforms, regions=None):
     """-> (pred, logit): the logits (or probabilities) resized back when `ori_shape` differs from their extent, then their
-    argmax"""
+    argmax, or with `regions` (a RegionSpec) the label map rebuilt from the thresholded region logits"""
     if ori_shape is not None and tuple(ori_shape) != tuple(logit.shape[2:]):
         logit = reverse_transform(logit, ori_shape, transforms, mode='bilinear')
+    if regions is not None:
+        return regions.to_label(logit), logit
     pred = _new_pred(logit)
     logit.dev.call("msk_argmax_c", logit.msk(), C.c_void_p(pred.ptr))
     return pred, logit
@@ -152,7 +158,7 @@ def tta_release(dev):
     _release(dev, "tta")
 
 
-def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_axes=(), with_plain=False):
+def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_axes=(), with_plain=False, regions=None):
     """Flip- and scale-averaged prediction: one forward per pass of tta_passes(scales, flip_axes), the softmax of every pass
     mirrored back and summed on the device in pass order (msk_tta_accumulate: no mirrored copy, no probabilities in
     between), then the mean and its argmax (msk_tta_finish).  A pass at scale != 1 resizes `im` to tta_size with the
@@ -165,7 +171,13 @@ def aug_inference(model, im, ori_shape=None, transforms=None, scales=1.0, flip_a
     computes before its reverse_transform -- and needs 1.0 among `scales`.
 
     Runs in one nn.fused_inference scope.  The returned tensors are valid until the next forward, as inference()'s are.
-    A model's own errors at sizes it cannot run (a scaled extent its strides do not divide) propagate unchanged."""
+    A model's own errors at sizes it cannot run (a scaled extent its strides do not divide) propagate unchanged.
+
+    What is averaged are softmax probabilities, which region-based (sigmoid) channels do not have: `regions` raises ValueError
+    (sliding_window_inference(mirror_axes=...) averages logits and takes regions)."""
+    if regions is not None:
+        raise ValueError("aug_inference averages softmax probabilities and does not support regions; "
+                         "use sliding_window_inference(mirror_axes=..., regions=...)")
     passes = tta_passes(scales, flip_axes)
     if with_plain and (1.0, 0) not in passes:
         raise ValueError("aug_inference(with_plain=True) needs 1.0 among scales, got %r" % (scales,))
@@ -329,7 +341,7 @@ def sliding_release(dev):
 
 
 def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', sigma_scale=0.125, sw_batch_size=1, cval=0.0,
-                             ori_shape=None, transforms=None, mirror_axes=()):
+                             ori_shape=None, transforms=None, mirror_axes=(), regions=None):
     """Window-by-window prediction at native resolution: the net runs on the overlapping `roi_size` windows of SlidingPlan
     (`overlap`, implicit padding with `cval` where the volume is smaller than the window), sw_batch_size windows per forward
     (the last batch may be smaller), and the outputs are blended on the device with the plan's normalised window weights
@@ -353,7 +365,10 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
     are the list [(window, mask) for window in windows for mask in masks]; sw_batch_size then counts PASSES per forward, and a
     window's passes may straddle two forwards: msk_sw_gather_mirrored -> model(patches)[0] -> one
     msk_sw_accumulate_mirrored(scale = 1 / K) per batch.  Every pass is one add at a fixed place in the sequence, so the
-    result does not depend on sw_batch_size.  Without mirror_axes the calls are those described above, unchanged."""
+    result does not depend on sw_batch_size.  Without mirror_axes the calls are those described above, unchanged.
+
+    regions (a RegionSpec with class_order): the prediction is rebuilt from the thresholded blended logits
+    (msk_regions_to_label) instead of their argmax, as in inference(); what is blended and mirrored stays the logits."""
     if not isinstance(sw_batch_size, (int, np.integer)) or isinstance(sw_batch_size, bool) or sw_batch_size < 1:
         raise ValueError("sliding_window_inference: sw_batch_size must be a positive integer, got %r" % (sw_batch_size,))
     masks = [m for _, m in tta_passes(1.0, mirror_axes)]
@@ -395,4 +410,4 @@ def sliding_window_inference(model, im, roi_size, overlap=0.5, mode='gaussian', 
             else:
                 dev.call("msk_sw_accumulate", logit.msk(), origins.ctypes.data_as(C.c_void_p), C.c_void_p(td), rows[0],
                          C.c_void_p(th), rows[1], C.c_void_p(tw), rows[2], acc.msk())
-    return _finish(_restamp(acc), ori_shape, transforms)
+    return _finish(_restamp(acc), ori_shape, transforms, regions)

@@ -46,8 +46,17 @@ def _image_info(dataset_json, idx):
 def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_roc=False, writer=None,
              save_dir=None, hard_metrics=False, pred_transform=None, auc_device=False, surface_metrics=False,
              surface_spacing=None, aug_eval=False, scales=1.0, flip_axes=(), sliding_window=None, sw_overlap=0.5,
-             sw_mode='gaussian', sw_batch_size=1, sw_mirror_axes=()):
-    """sliding_window: a roi (rd, rh, rw); the logits and the prediction of every volume come from
+             sw_mode='gaussian', sw_batch_size=1, sw_mirror_axes=(), regions=None):
+    """regions (region-based training): a RegionSpec with class_order; by default ``losses['types'][0].region_spec`` when
+    the loss has one (DiceBCERegionLoss), so validation during training and val.py need no option.  The model's channels are
+    then sigmoid regions: the hard-label prediction is rebuilt from the thresholded logits (``inference(regions=...)`` /
+    ``sliding_window_inference(regions=...)``), ``mdice`` is the per-region soft Dice of the loss, and ``hard_metrics`` adds
+    region_dice (mean over the regions of the Dice pooled over the set), class_region_dice (per region) and
+    region_dice_per_case (mean over volumes of the region-mean Dice), computed on the host in exact integers from the
+    confusion counts already taken (utils.metric.region_areas_from_counts).  ``auc_roc`` and ``aug_eval`` need softmax
+    probabilities: together with regions they raise ValueError.
+
+    sliding_window: a roi (rd, rh, rw); the logits and the prediction of every volume come from
     ``infer.sliding_window_inference(roi_size=sliding_window, overlap=sw_overlap, mode=sw_mode, sw_batch_size=sw_batch_size,
     mirror_axes=sw_mirror_axes)`` -- the net on overlapping windows at the volume's own resolution, blended on the device -- in
     place of the one forward of ``infer.inference``; everything downstream (loss, mdice, hard and surface metrics, AUC, saved
@@ -83,6 +92,14 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
     multi-volume file yields several arrays under other names), and neither the json nor the dataset records which
     array axis it belongs to after the remaining preparation steps -- the 'xyz' of the saved NIfTI files above is an
     assumption of this loop, not a recorded fact.  ignore_index gets no special treatment."""
+    if regions is None:
+        regions = getattr(losses['types'][0], 'region_spec', None)
+    if regions is not None:
+        if auc_roc or aug_eval:
+            raise ValueError("evaluate: auc_roc=True and aug_eval=True score softmax probabilities and are not supported "
+                             "together with regions")
+        if getattr(regions, 'class_order', None) is None:
+            raise ValueError("evaluate: regions needs a RegionSpec with class_order")
     if aug_eval and (1.0, 0) not in infer.tta_passes(scales, flip_axes):
         raise ValueError("evaluate(aug_eval=True): scales must contain 1.0 (mdice and the loss are the plain pass's), got %r"
                          % (scales,))
@@ -93,6 +110,7 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         raise ValueError("evaluate: sw_mirror_axes=%r needs sliding_window (aug_eval mirrors whole volumes)" % (sw_mirror_axes,))
     infer.tta_passes(1.0, sw_mirror_axes)            # a bad or duplicate axis raises here, before any work
 
+    region_kw = {} if regions is None else {"regions": regions}      # without regions the calls are what they were
     # the chosen prediction path as one callable -> (pred, logits, mean_probs or None)
     if aug_eval:
         def predict(im, ori_shape):
@@ -107,10 +125,11 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
             return infer.sliding_window_inference(model, im, sliding_window, overlap=sw_overlap, mode=sw_mode,
                                                   sw_batch_size=sw_batch_size, ori_shape=ori_shape,
                                                   transforms=eval_dataset.transforms.transforms,
-                                                  mirror_axes=sw_mirror_axes) + (None,)
+                                                  mirror_axes=sw_mirror_axes, **region_kw) + (None,)
     else:
         def predict(im, ori_shape):
-            return infer.inference(model, im, ori_shape=ori_shape, transforms=eval_dataset.transforms.transforms) + (None,)
+            return infer.inference(model, im, ori_shape=ori_shape, transforms=eval_dataset.transforms.transforms,
+                                   **region_kw) + (None,)
     new_loss = {'types': [losses['types'][0]], 'coef': [losses['coef'][0]]}
     if writer is not None:
         logger.warning("evaluate(writer=...): VisualDL logging is not built; the writer is ignored.")
@@ -210,6 +229,16 @@ def evaluate(model, eval_dataset, losses, num_workers=0, print_detail=True, auc_
         hard_infor = ("[EVAL] Hard labels: mIoU: {:.4f}, Dice: {:.4f}, Dice per case: {:.4f}, Acc: {:.4f}, Kappa: {:.4f}".format(
             miou, hdice, dice_per_case, acc, kappa),
             "[EVAL] Class IoU: \n" + str(np.round(class_iou, 4)) + "\n[EVAL] Class hard dice: \n" + str(np.round(class_dice, 4)))
+        if regions is not None:
+            table, R = regions.table(), regions.num_regions
+            class_region_dice, region_dice = metric.dice(*metric.region_areas_from_counts(c, num_classes, table, R))
+            rows = metric.region_areas_from_counts(c, num_classes, table, R, per_volume=True)
+            region_dice_per_case = float(np.mean([metric.dice(i, p, l)[1] for i, p, l in zip(*rows)]))
+            result_dict.update(region_dice=float(region_dice), class_region_dice=class_region_dice,
+                               region_dice_per_case=region_dice_per_case)
+            hard_infor = (hard_infor[0] + ", Region Dice: {:.4f}, Region Dice per case: {:.4f}".format(
+                region_dice, region_dice_per_case),
+                hard_infor[1] + "\n[EVAL] Region hard dice: \n" + str(np.round(class_region_dice, 4)))
     surface_infor = None
     if surface_metrics and surface_cases:
         ss = metric.surface_summary(surface_cases)

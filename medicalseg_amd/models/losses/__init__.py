@@ -4,5 +4,6 @@ from .dice_loss import DiceLoss
 from .mixes_losses import MixedLoss
 from .binary_cross_entropy_loss import BCELoss
 from .region_losses import DiceCELoss, FocalLoss, SoftDiceLoss, TverskyLoss
+from .region_based_losses import DiceBCERegionLoss, RegionSpec
 from .topk_losses import DiceTopKLoss, TopKLoss
 from .boundary_losses import BoundaryLoss, DiceBoundaryLoss

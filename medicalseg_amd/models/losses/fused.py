@@ -204,6 +204,34 @@ class RegionNode(Node):
                       accumulate, dz.msk())
 
 
+class MultiLabelNode(Node):
+    """Sigmoid Dice + BCE over label regions (the 'bce' term, out[0], and the 'dice' term, out[1]; out[2:] is the per-region
+    Dice): msk_mlabel_loss_fwd / msk_mlabel_loss_bwd, one statistics pass and one gradient pass for both terms.  The channels
+    of the logits are the regions; the label stays one int32 per voxel.  `settings` is (ignore_index, squared_pred, batch_dice,
+    smooth, table pointer, table length): the device table of uint32 that maps a label value to the bit mask of its regions
+    (RegionSpec.device_table).  With several ranks the sums are those of this rank's batch."""
+    SLOTS = {"bce": 0, "dice": 1}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.ignore_index, self.squared_pred, self.batch_dice, self.smooth, self.table_ptr, self.table_len = settings
+        self.groups = 1 if self.batch_dice else logits.n
+
+    def stats_doubles(self):
+        return 5 * self.groups * self.C + 2
+
+    def _args(self):
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(self.ignore_index), C.c_void_p(self.table_ptr),
+                int(self.table_len), int(self.squared_pred), int(self.batch_dice), C.c_float(self.smooth))
+
+    def _forward(self):
+        self.dev.call("msk_mlabel_loss_fwd", *self._args(), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef_bce, coef_dice, accumulate, dz):
+        self.dev.call("msk_mlabel_loss_bwd", *self._args(), C.c_void_p(self.stats_ptr), C.c_float(coef_bce), C.c_float(coef_dice),
+                      accumulate, dz.msk())
+
+
 class TopKNode(Node):
     """Top-k cross entropy (the 'topk' term, out[0]): msk_topk_ce_fwd / msk_topk_ce_bwd.  `settings` is (ignore_index, k,
     weight_ptr): k the percentage of the valid voxels that count, weight_ptr the device vector of per-class weights or None.

@@ -6,7 +6,8 @@ user-defined losses with those names take the same branches."""
 from ..device import Tensor
 
 _EDGE_LOSSES = ('BCELoss', 'FocalLoss')
-_DICE_LOSSES = ('DiceLoss', 'SoftDiceLoss', 'TverskyLoss', 'DiceCELoss', 'DiceTopKLoss', 'DiceBoundaryLoss')   # they return (loss, per_channel_dice)
+_DICE_LOSSES = ('DiceLoss', 'SoftDiceLoss', 'TverskyLoss', 'DiceCELoss', 'DiceTopKLoss', 'DiceBoundaryLoss',
+                'DiceBCERegionLoss')   # they return (loss, per_channel_dice)
 
 
 def check_logits_losses(logits_list, losses):

@@ -381,6 +381,30 @@ def areas_from_counts(counts, num_classes, ignore_index=255, per_volume=False):
     return intersect.sum(axis=0), pred_area.sum(axis=0), label_area.sum(axis=0)
 
 
+def region_areas_from_counts(counts, num_classes, table, num_regions, per_volume=False):
+    """(intersect_area, pred_area, label_area) per REGION from the same confusion counts (region-based training: the regions
+    overlap, so they are no partition of the classes): int64 arrays of length num_regions summed over the rows, or
+    [N, num_regions] with ``per_volume``.  Class c < num_classes belongs to region r when bit r of table[c] is set
+    (RegionSpec.table()); the "other" class (a value outside [0, num_classes)) belongs to no region.  intersect counts the
+    voxels whose label AND prediction lie in the region, pred_area / label_area those whose prediction / label does; the
+    ignored voxels count nowhere.  Exact integers on the host (tests/mlabel_reference.py: region_areas)."""
+    num_classes, num_regions = int(num_classes), int(num_regions)
+    K = num_classes + 1
+    table = np.asarray(table)
+    c = _host(counts).astype(np.int64).reshape(-1, K * K + 1)
+    m = c[:, :K * K].reshape(-1, K, K)                       # [volume, label class, predicted class]
+    member = np.zeros((num_regions, K), dtype=np.int64)      # [region, class]; the last column (other) stays 0
+    for cls in range(min(num_classes, table.size)):
+        for r in range(num_regions):
+            member[r, cls] = (int(table[cls]) >> r) & 1
+    label_area = np.einsum('nlp,rl->nr', m, member)
+    pred_area = np.einsum('nlp,rp->nr', m, member)
+    intersect = np.einsum('nlp,rl,rp->nr', m, member, member)
+    if per_volume:
+        return intersect, pred_area, label_area
+    return intersect.sum(axis=0), pred_area.sum(axis=0), label_area.sum(axis=0)
+
+
 def calculate_area(pred, label, num_classes, ignore_index=255):
     """metric.py:21-61 -> (intersect_area, pred_area, label_area), int64 [num_classes], summed over the batch.
     Device inputs are counted on the device (one download of the counts)."""
