@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Imedicalseg_amd/csr
 OBJS=""
 for f in medicalseg_amd/csrc/*.hip; do
   o=build/$(basename ${f%.hip}).o
-  if [ ! -f $o ] || [ $f -nt $o ] || [ include/msegk.h -nt $o ] || [ medicalseg_amd/csrc/msk_common.h -nt $o ] || [ medicalseg_amd/csrc/msk_device.h -nt $o ] || [ medicalseg_amd/csrc/msk_conv.h -nt $o ] || [ medicalseg_amd/csrc/msk_wbf.h -nt $o ]; then
+  if [ ! -f $o ] || [ $f -nt $o ] || [ include/msegk.h -nt $o ] || [ medicalseg_amd/csrc/msk_common.h -nt $o ] || [ medicalseg_amd/csrc/msk_device.h -nt $o ] || [ medicalseg_amd/csrc/msk_conv.h -nt $o ] || [ medicalseg_amd/csrc/msk_wbf.h -nt $o ] || [ medicalseg_amd/csrc/msk_pack.h -nt $o ] || [ medicalseg_amd/csrc/msk_pack_rows.h -nt $o ]; then
     rm -f $o   # a failed compile must not leave the previous object behind (the jobs run in the background)
     hipcc $FLAGS $EXTRA -c $f -o $o &
   fi

@@ -24,6 +24,14 @@ struct msk_pending_event {
   const char* tag;
 };
 
+// A packed-weight cache as the weight hooks see it (msk_pack.h implements these over one row table)
+struct msk_pack_cache {
+  virtual ~msk_pack_cache() {}                                  // frees the images and the device tables
+  virtual void changed(const void* p, size_t bytes) = 0;        // [p, p + bytes) was written
+  virtual void freed(msk_ctx* ctx, const void* p, size_t bytes) = 0;
+  virtual int prepack(msk_ctx* ctx, const void* p, size_t bytes) = 0;   // p == nullptr: every stale row in use; the use epoch ends
+};
+
 struct msk_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -72,9 +80,9 @@ struct msk_ctx {
   int scalar_next_side = 0;
   long scalar_served_side = 0;
   int wbf_tpb = 0;            // wbf_gemm_k: tiles per workgroup (0 = 1)
-  void* wpack = nullptr;      // packed-weight cache of the Winograd pipelines (msk_conv_wbf.hip: WbfPackCache)
+  msk_pack_cache* wpack = nullptr;   // packed-weight cache of the Winograd pipelines (msk_conv_wbf.hip: WbfPackCache)
   int wbf_pack_cache = 1;     // 0 = pack the weights on every call (A/B)
-  void* spack = nullptr;      // packed-weight cache of the other convolution kernels (msk_conv.hip: SmallPackCache)
+  msk_pack_cache* spack = nullptr;   // packed-weight cache of the other convolution kernels (msk_conv.hip: SmallPackCache)
   int wbf_pack_lds = 1;       // option "wbf_pack_lds": packed Winograd weights through an LDS tile with whole-run loads and 16-byte stores (wbf_pack_weights_lds_k); 0 = one thread per element (A/B)
   int wbf_bpf = 1;            // option "wbf_bpf": weight-fragment prefetch depth of wbf_gemm_k: 1 (default), 4 = four taps ahead, 0 = 4 for launches of <= 8 workgroups per CU (round 5 A/B: 18.45 ms with 1, 18.58 with 0 / 4 -- the deeper ring costs more than the waits it removes)
   int wbf_fused_sh = 1;       // option "wbf_fused_sh": MFMA shape of the pipelined one-kernel matrix stage with 32 output channels: 1 = 16x16x32 over tap pairs, 0 = 32x32x16 (A/B, tests)
@@ -177,16 +185,12 @@ void msk_set_reduce_vpl(int v);
 void msk_set_reduce_vpl_site(int v);   // option "reduce_vpl_site"          // option "reduce_vpl"
 void msk_set_ew_caps(int ew, int red);   // msk_elementwise.hip tuning knobs
 int msk_get_ew_option(const char* key, int* value);   // "ew_cap", "reduce_cap", "reduce_vpl", "dense12" as they stand: 1 = known key
-// caller memory that may hold convolution weights was (or is about to be) written / freed: derived forms are stale
+// caller memory that may hold convolution weights was (or is about to be) written / freed: derived forms are stale.  These
+// walk both packed-weight caches of the context (msk_ctx.hip; msk_pack.h)
 void msk_weights_changed_impl(msk_ctx* ctx, const void* p, size_t bytes);
 void msk_weights_freed_impl(msk_ctx* ctx, const void* p, size_t bytes);  // msk_free: drop the rows inside [p, p + bytes)
-int msk_wbf_prepack_impl(msk_ctx* ctx);   // rebuild every stale packed-weight row in use (end of the optimizer kernels)
-int msk_wbf_prepack_range_impl(msk_ctx* ctx, const void* p, size_t bytes);   // the stale rows inside [p, p + bytes), current stream
-void msk_wbf_pack_cache_free(msk_ctx* ctx);
-void msk_small_pack_changed(msk_ctx* ctx, const void* p, size_t bytes);   // SmallPackCache hooks (msk_conv.hip), called by the *_impl functions above
-void msk_small_pack_freed(msk_ctx* ctx, const void* p, size_t bytes);
-int msk_small_prepack(msk_ctx* ctx, const void* p, size_t bytes);        // p == nullptr: every stale row in use
-void msk_small_pack_free(msk_ctx* ctx);
+int msk_prepack_impl(msk_ctx* ctx);   // rebuild every stale packed-weight row in use (end of the optimizer kernels)
+int msk_prepack_range_impl(msk_ctx* ctx, const void* p, size_t bytes);   // the stale rows inside [p, p + bytes), current stream
 int msk_dp_wait_impl(msk_ctx* ctx);
 // msk_edt3d's checks and passes (msk_edt.hip); complement != 0: the features are {vol != cls} (msk_label_sdf)
 int msk_edt_field(msk_ctx* ctx, const int32_t* vol, int d, int h, int w, int cls, int surface_only, int complement,

@@ -4,6 +4,7 @@
 // The six public ops (Conv3D fwd/dgrad/wgrad, Conv3DTranspose fwd/dgrad/wgrad) reduce to
 // two device problems (msk_conv.h): a "gather convolution" and a weight gradient.
 #include "msk_conv.h"
+#include "msk_pack.h"
 #include "msk_wbf.h"
 
 namespace {
@@ -60,11 +61,10 @@ pack_weights_k(const float* __restrict__ w, int A, int B, int taps, int swap, in
 // Round 5: the packed images of the non-Winograd kernels are CACHED (the Winograd pipelines have had WbfPackCache since round 3).
 // Every call of a kernel == stride convolution, a gather kernel or a 1x1x1 head used to launch its own 5-us pack kernel in
 // front of the convolution: 20 launches per VNet step on the compute stream.  A row = (canonical weight pointer, layout
-// parameters) -> persistent device image; rows go stale through the same hooks as the Winograd rows (msk_weights_changed_impl /
-// msk_weights_freed_impl) and are rebuilt TOGETHER, one launch over a device-side descriptor table (blockIdx.y = row), where
-// the Winograd rows are: at the end of the optimizer kernels (msk_wbf_prepack_impl; per slice on the optimizer's stream in the
-// eager form, msk_wbf_prepack_range_impl).  A row that is still stale when a convolution asks for it is rebuilt alone, on the
-// asking stream.  kind 0: pack_weights_k layouts; kind 1: the scatter layout Bf[kc][h][jpad][4] (msk_conv_scatter.hip).
+// parameters) -> persistent device image.  Bookkeeping, eviction, invalidation and the rebuild by the optimizer kernels are
+// those of every packed-weight cache (msk_pack.h); what is this cache's own: 128 rows, and ONE rebuild launch over a
+// device-side descriptor table (blockIdx.y = row).  A row that is still stale when a convolution asks for it is rebuilt alone,
+// on the asking stream.  kind 0: pack_weights_k layouts; kind 1: the scatter layout Bf[kc][h][jpad][4] (msk_conv_scatter.hip).
 // ---------------------------------------------------------------------------
 struct SmallPackDesc {
   const float* w;
@@ -76,17 +76,25 @@ struct SmallPackList {
   int n;
   unsigned char rows[60];
 };
-struct SmallPackEntry {
+struct SmallPackRow {
   SmallPackDesc d{};
-  size_t bytes = 0;
-  bool live = false, valid = false;
-  long last_use = 0;
+  const void* weights() const { return d.w; }
+  size_t weight_bytes() const { return (size_t)d.A * d.B * d.taps * sizeof(float); }
+  void* image() const { return d.out; }
+  bool same_key(const SmallPackRow& o) const {
+    const SmallPackDesc& a = d;
+    const SmallPackDesc& b = o.d;
+    return a.w == b.w && a.kind == b.kind && a.A == b.A && a.B == b.B && a.taps == b.taps && a.swap == b.swap && a.flip == b.flip &&
+           a.kd == b.kd && a.kh == b.kh && a.kw == b.kw && a.mfma == b.mfma && a.K == b.K && a.N == b.N && a.KC == b.KC &&
+           a.npad == b.npad;
+  }
 };
-struct SmallPackCache {
-  static constexpr int kRows = 128;
-  SmallPackEntry e[kRows];
+struct SmallPackCache : PackCache<SmallPackRow, 128> {
   SmallPackDesc* table = nullptr;   // device copy of the descriptors
-  long tick = 0;
+  SmallPackDesc& desc(int r) { return rows.e[r].d.d; }
+  int build(msk_ctx* ctx, const std::vector<int>& which) override;
+  void store(msk_ctx* ctx, int r, void* image) override;
+  ~SmallPackCache() override { (void)hipFree(table); }
 };
 
 __global__ void small_pack_desc_store_k(SmallPackDesc* slot, SmallPackDesc d) { *slot = d; }
@@ -120,33 +128,31 @@ small_pack_batch_k(const SmallPackDesc* __restrict__ table, SmallPackList l) {
   }
 }
 
-bool small_pack_same(const SmallPackDesc& a, const SmallPackDesc& b) {
-  return a.w == b.w && a.kind == b.kind && a.A == b.A && a.B == b.B && a.taps == b.taps && a.swap == b.swap && a.flip == b.flip &&
-         a.kd == b.kd && a.kh == b.kh && a.kw == b.kw && a.mfma == b.mfma && a.K == b.K && a.N == b.N && a.KC == b.KC &&
-         a.npad == b.npad;
-}
-
-int small_pack_build(msk_ctx* ctx, SmallPackCache* c, const std::vector<int>& rows) {
-  for (size_t i0 = 0; i0 < rows.size(); i0 += sizeof(SmallPackList::rows)) {
+int SmallPackCache::build(msk_ctx* ctx, const std::vector<int>& which) {
+  for (size_t i0 = 0; i0 < which.size(); i0 += sizeof(SmallPackList::rows)) {
     SmallPackList l{};
     long most = 0;
-    for (size_t i = i0; i < rows.size() && l.n < (int)sizeof(l.rows); ++i) {
-      l.rows[l.n++] = (unsigned char)rows[i];
-      if (c->e[rows[i]].d.total > most) most = c->e[rows[i]].d.total;
+    for (size_t i = i0; i < which.size() && l.n < (int)sizeof(l.rows); ++i) {
+      l.rows[l.n++] = (unsigned char)which[i];
+      if (desc(which[i]).total > most) most = desc(which[i]).total;
     }
     long gx = (most + kThreads - 1) / kThreads;
     if (gx > 2L * ctx->num_cu) gx = 2L * ctx->num_cu;
     if (gx < 1) gx = 1;
     msk_launch_scope ls(ctx, "pack_weights_batch");
-    hipLaunchKernelGGL(small_pack_batch_k, dim3((unsigned)gx, (unsigned)l.n), dim3(kThreads), 0, ctx->stream, c->table, l);
+    hipLaunchKernelGGL(small_pack_batch_k, dim3((unsigned)gx, (unsigned)l.n), dim3(kThreads), 0, ctx->stream, table, l);
     MSK_LAUNCH_CHECK(ctx);
-    for (int i = 0; i < l.n; ++i) c->e[l.rows[i]].valid = true;
+    for (int i = 0; i < l.n; ++i) rows.e[l.rows[i]].valid = true;
   }
   return 0;
 }
+void SmallPackCache::store(msk_ctx* ctx, int r, void* image) {
+  desc(r).out = (float*)image;
+  hipLaunchKernelGGL(small_pack_desc_store_k, dim3(1), dim3(1), 0, ctx->stream, table + r, desc(r));
+}
 
-// the cached image of a row (created on first use); nullptr on failure (error set)
-const float* small_pack_get(msk_ctx* ctx, SmallPackDesc key, size_t bytes) {
+// the cached image of a key (its row is created on first use); nullptr on failure (error set)
+const float* small_pack_get(msk_ctx* ctx, const SmallPackRow& key, size_t bytes) {
   if (!ctx->spack) {
     SmallPackCache* nc = new SmallPackCache();
     if (hipMalloc((void**)&nc->table, sizeof(SmallPackDesc) * SmallPackCache::kRows) != hipSuccess) {
@@ -156,68 +162,11 @@ const float* small_pack_get(msk_ctx* ctx, SmallPackDesc key, size_t bytes) {
     }
     ctx->spack = nc;
   }
-  SmallPackCache* c = (SmallPackCache*)ctx->spack;
-  c->tick += 1;
-  int row = -1, free_row = -1, lru = -1;
-  for (int r = 0; r < SmallPackCache::kRows; ++r) {
-    SmallPackEntry& e = c->e[r];
-    if (!e.live) {
-      if (free_row < 0) free_row = r;
-      continue;
-    }
-    if (small_pack_same(e.d, key)) {
-      row = r;
-      break;
-    }
-    if (lru < 0 || e.last_use < c->e[lru].last_use) lru = r;
-  }
-  if (row < 0) {
-    row = free_row >= 0 ? free_row : lru;
-    SmallPackEntry& e = c->e[row];
-    // a row keeps its image's allocation across tenants (stream order protects a reused image: it is rewritten on the stream
-    // whose kernels read it, or behind that stream's tail); a larger one is allocated behind everything in flight
-    float* out = e.d.out;
-    if (out && e.live && ctx->side != nullptr) {
-      // a live row changes tenant (all rows in use: LRU): its image and descriptor are rewritten on THIS stream -- the other
-      // stream may still hold launches that read the old tenant's image, so this one waits for the other's current tail first
-      // (rare: more than kRows live weight images; advisor, round 5)
-      static thread_local hipEvent_t ev = nullptr;
-      if (!ev) hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (ev) {
-        hipEventRecord(ev, ctx->side);
-        hipStreamWaitEvent(ctx->stream, ev, 0);
-      }
-    }
-    if (out && e.bytes < bytes) {
-      hipStreamSynchronize(ctx->stream);
-      if (ctx->side) hipStreamSynchronize(ctx->side);
-      hipFree(out);
-      out = nullptr;
-      e.d.out = nullptr;
-      e.bytes = 0;
-    }
-    if (!out) {
-      if (hipMalloc((void**)&out, bytes) != hipSuccess) {
-        e.live = false;
-        msk_fail(ctx, __FILE__, __LINE__, "small_pack_get", "hipMalloc failed");
-        return nullptr;
-      }
-      e.bytes = bytes;
-    }
-    e.d = key;
-    e.d.out = out;
-    e.live = true;
-    e.valid = false;
-    hipLaunchKernelGGL(small_pack_desc_store_k, dim3(1), dim3(1), 0, ctx->stream, c->table + row, e.d);
-    if (hipGetLastError() != hipSuccess) {
-      msk_fail(ctx, __FILE__, __LINE__, "small_pack_get", "kernel launch");
-      return nullptr;
-    }
-  }
-  SmallPackEntry& e = c->e[row];
-  e.last_use = c->tick;
-  if (!e.valid && small_pack_build(ctx, c, std::vector<int>{row}) != 0) return nullptr;
-  return e.d.out;
+  SmallPackCache* c = static_cast<SmallPackCache*>(ctx->spack);
+  const int row = c->row_of(ctx, key, bytes);
+  if (row < 0) return nullptr;
+  if (!c->rows.e[row].valid && c->build(ctx, std::vector<int>{row}) != 0) return nullptr;
+  return c->desc(row).out;
 }
 
 // ---------------------------------------------------------------------------
@@ -1129,76 +1078,20 @@ const float* msk_pack_weights_get(msk_ctx* ctx, const float* w, int A, int B, in
     if (!out) return nullptr;
     return msk_pack_weights(ctx, w, A, B, taps, swap, flip_taps, kd, kh, kw, mfma, K, N, KC, npad, out) == 0 ? out : nullptr;
   }
-  SmallPackDesc d{};
+  SmallPackRow key;
+  SmallPackDesc& d = key.d;
   d.w = w; d.total = total; d.kind = 0; d.A = A; d.B = B; d.taps = taps; d.swap = swap; d.flip = flip_taps;
   d.kd = kd; d.kh = kh; d.kw = kw; d.mfma = mfma; d.K = K; d.N = N; d.KC = KC; d.npad = npad;
-  return small_pack_get(ctx, d, (size_t)total * sizeof(float));
+  return small_pack_get(ctx, key, (size_t)total * sizeof(float));
 }
 // the scatter layout of msk_conv_scatter.hip, cached the same way (the caller packs itself when this returns nullptr with the cache off)
 const float* msk_pack_scatter_get(msk_ctx* ctx, const float* w, int A, int B, int taps, int swap, int CK, int CN, int KC, int jpad) {
   if (!ctx->small_pack_cache) return nullptr;
-  SmallPackDesc d{};
+  SmallPackRow key;
+  SmallPackDesc& d = key.d;
   d.w = w; d.total = (long)KC * 2 * jpad; d.kind = 1; d.A = A; d.B = B; d.taps = taps; d.swap = swap;
   d.K = CK; d.N = CN; d.KC = KC; d.npad = jpad;
-  return small_pack_get(ctx, d, (size_t)d.total * 4 * sizeof(float));
-}
-void msk_small_pack_changed(msk_ctx* ctx, const void* p, size_t bytes) {
-  if (!ctx->spack || !p) return;
-  SmallPackCache* c = (SmallPackCache*)ctx->spack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  for (int r = 0; r < SmallPackCache::kRows; ++r) {
-    SmallPackEntry& e = c->e[r];
-    if (!e.live) continue;
-    const char* b0 = (const char*)e.d.w;
-    const char* b1 = b0 + (size_t)e.d.A * e.d.B * e.d.taps * sizeof(float);
-    if (a0 < b1 && b0 < a1) e.valid = false;
-  }
-}
-void msk_small_pack_freed(msk_ctx* ctx, const void* p, size_t bytes) {
-  if (!ctx->spack || !p) return;
-  SmallPackCache* c = (SmallPackCache*)ctx->spack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  for (int r = 0; r < SmallPackCache::kRows; ++r) {
-    SmallPackEntry& e = c->e[r];
-    if (!e.live) continue;
-    const char* b0 = (const char*)e.d.w;
-    const char* b1 = b0 + (size_t)e.d.A * e.d.B * e.d.taps * sizeof(float);
-    if (bytes ? (a0 < b1 && b0 < a1) : b0 == a0) {   // the image stays allocated for the row's next tenant
-      e.live = false;
-      e.valid = false;
-      e.d.w = nullptr;
-    }
-  }
-}
-// rebuild the stale rows in use (all of them, or those whose weights lie wholly inside [p, p + bytes)) in one launch on the current stream
-int msk_small_prepack(msk_ctx* ctx, const void* p, size_t bytes) {
-  if (!ctx->spack) return 0;
-  SmallPackCache* c = (SmallPackCache*)ctx->spack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  std::vector<int> rows;
-  for (int r = 0; r < SmallPackCache::kRows; ++r) {
-    const SmallPackEntry& e = c->e[r];
-    if (!e.live || e.valid || e.last_use + 4096 < c->tick) continue;   // rows nothing has asked for in a long while wait for their next use
-    if (p) {
-      const char* b0 = (const char*)e.d.w;
-      const char* b1 = b0 + (size_t)e.d.A * e.d.B * e.d.taps * sizeof(float);
-      if (!(b0 >= a0 && b1 <= a1)) continue;
-    }
-    rows.push_back(r);
-  }
-  return rows.empty() ? 0 : small_pack_build(ctx, c, rows);
-}
-void msk_small_pack_free(msk_ctx* ctx) {
-  if (!ctx->spack) return;
-  SmallPackCache* c = (SmallPackCache*)ctx->spack;
-  for (int r = 0; r < SmallPackCache::kRows; ++r)
-    if (c->e[r].d.out) hipFree(c->e[r].d.out);
-  if (c->table) hipFree(c->table);
-  delete c;
-  ctx->spack = nullptr;
+  return small_pack_get(ctx, key, (size_t)d.total * 4 * sizeof(float));
 }
 
 // float4 variant (CB % 4 == 0): a lane owns 4 consecutive cb of one (tap, ca) row -> 1 KiB per wavefront load,

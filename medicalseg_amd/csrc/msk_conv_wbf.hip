@@ -33,6 +33,7 @@
 //   U [xi][tap][kc][piece][khalf][CN]        B fragment of lane (khalf, co) is one contiguous slot
 //   M [ks][xi][n][t][d][h][CN] fp32
 #include <type_traits>
+#include "msk_pack.h"
 #include "msk_wbf.h"
 #ifndef WBF_TIN_SYNC
 #define WBF_TIN_SYNC 1   // transform kernels: one barrier per W tile keeps a block's four wavefronts on the same 128-byte lines (0 = A/B)
@@ -2116,32 +2117,51 @@ void launch_gemm_variant(msk_ctx* ctx, const char* tag, int variant, const GemmA
 // Packed-weight cache (round 3).  The transformed + split weights U of a layer depend on the weights only, and those
 // change once per optimizer step -- not per call: every (weights, direction, geometry) combination owns a table row with
 // a persistent U buffer and the amax array of its weights.  A row is rebuilt (absmax + pack)
-//   * for ALL rows in use at once, two launches, at the end of msk_sgd_momentum / msk_adam (msk_wbf_prepack): 28 pack
+//   * for ALL rows in use at once, two launches, at the end of msk_sgd_momentum / msk_adam (msk_prepack_impl): 28 pack
 //     launches + 14 absmax passes + their memsets per step became 2 + 1;
 //   * lazily at its next use otherwise.
 // Rows are invalidated by every entry point that writes caller memory which may hold weights (msk_weights_changed:
 // optimizer kernels, msk_h2d / msk_h2d_async / msk_memset / msk_d2d, msk_conv_fold_bn, msk_dp_broadcast, msk_free).
+// Bookkeeping, eviction, invalidation and the rebuild hooks are those of every packed-weight cache (msk_pack.h); what is this
+// cache's own: 249 rows, an amax slot per row (addressed by row number), the pack kernels per (K, NP) class, and the scratch
+// entry of uncached calls -- row number kScratch with the last amax slot, no table slot: it is rebuilt on every call.
 // ---------------------------------------------------------------------------------------------------------
-struct WbfPackEntry {
+struct WbfPackRow {
   WbfPackDesc d{};
   int K = 0, NP = 0;
-  size_t u_bytes = 0;
-  bool live = false, valid = false;
-  long last_use = 0;
+  const void* weights() const { return d.w; }
+  size_t weight_bytes() const { return (size_t)d.count * sizeof(float); }
+  void* image() const { return d.out; }
+  bool same_key(const WbfPackRow& o) const {
+    const WbfPackDesc& k = o.d;
+    return d.w == k.w && K == o.K && NP == o.NP && d.A == k.A && d.B == k.B && d.swap == k.swap && d.flip == k.flip &&
+           d.CK == k.CK && d.CN == k.CN && d.KC == k.KC && d.tsd == k.tsd && d.tsh == k.tsh && d.tsw == k.tsw;
+  }
 };
-struct WbfPackCache {
-  static constexpr int kRows = 250;
-  WbfPackEntry e[kRows];
+struct WbfPackCache : PackCache<WbfPackRow, 249> {
+  static constexpr int kScratch = kRows;
+  WbfPackRow scratch;
   WbfPackDesc* table = nullptr;  // device copy of the descriptors
-  float* amax = nullptr;         // device [kRows][kWbfAmaxWays]
-  long epoch = 1;
+  float* amax = nullptr;         // device [kRows + 1][kWbfAmaxWays]
+  WbfPackRow& row(int r) { return r == kScratch ? scratch : rows.e[r].d; }
+  int build(msk_ctx* ctx, const std::vector<int>& which) override;
+  void store(msk_ctx* ctx, int r, void* image) override {
+    WbfPackDesc& d = row(r).d;
+    d.out = (unsigned short*)image;
+    d.amax = amax + (size_t)r * kWbfAmaxWays;
+    hipLaunchKernelGGL(wbf_pack_desc_store_k, dim3(1), dim3(1), 0, ctx->stream, table + r, d);  // no pageable-memory copy
+  }
+  ~WbfPackCache() override {
+    (void)hipFree(table);
+    (void)hipFree(amax);
+  }
 };
 
 WbfPackCache* pack_cache(msk_ctx* ctx) {
-  if (ctx->wpack) return (WbfPackCache*)ctx->wpack;
+  if (ctx->wpack) return static_cast<WbfPackCache*>(ctx->wpack);
   WbfPackCache* c = new WbfPackCache();
   if (hipMalloc((void**)&c->table, sizeof(WbfPackDesc) * WbfPackCache::kRows) != hipSuccess ||
-      hipMalloc((void**)&c->amax, sizeof(float) * kWbfAmaxWays * WbfPackCache::kRows) != hipSuccess) {
+      hipMalloc((void**)&c->amax, sizeof(float) * kWbfAmaxWays * (WbfPackCache::kRows + 1)) != hipSuccess) {
     msk_fail(ctx, __FILE__, __LINE__, "pack_cache", "hipMalloc failed");
     delete c;
     return nullptr;
@@ -2150,47 +2170,38 @@ WbfPackCache* pack_cache(msk_ctx* ctx) {
   return c;
 }
 
-void pack_row_drop(msk_ctx* ctx, WbfPackEntry& e) {
-  if (!e.live) return;
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->side) hipStreamSynchronize(ctx->side);
-  if (e.d.out) hipFree(e.d.out);
-  e = WbfPackEntry();
-}
-
 // rebuild the listed rows: zero their amax arrays, one absmax launch, one pack launch per (K, NP) class.  A single row
-// travels by value (its table slot may not be written yet / is the scratch row).
-int pack_rows_build(msk_ctx* ctx, WbfPackCache* c, const std::vector<int>& rows) {
-  if (rows.empty()) return 0;
-  const bool one = rows.size() == 1;
-  const WbfPackDesc single = c->e[rows[0]].d;
+// travels by value (its table slot may not be written yet / it is the scratch entry).
+int WbfPackCache::build(msk_ctx* ctx, const std::vector<int>& which) {
+  const bool one = which.size() == 1;
+  const WbfPackDesc single = row(which[0]).d;
   bool need_amax = false;
-  for (int r : rows) need_amax |= c->e[r].NP != 3;
+  for (int r : which) need_amax |= row(r).NP != 3;
   if (need_amax) {
     // zero the amax arrays of runs of consecutive rows with one memset each (in steady state: one run)
     size_t i = 0;
-    while (i < rows.size()) {
+    while (i < which.size()) {
       size_t j = i;
-      while (j + 1 < rows.size() && rows[j + 1] == rows[j] + 1) ++j;
-      MSK_CHECK_HIP(ctx, hipMemsetAsync(c->amax + (size_t)rows[i] * kWbfAmaxWays, 0, (j - i + 1) * kWbfAmaxWays * sizeof(float), ctx->stream));
+      while (j + 1 < which.size() && which[j + 1] == which[j] + 1) ++j;
+      MSK_CHECK_HIP(ctx, hipMemsetAsync(amax + (size_t)which[i] * kWbfAmaxWays, 0, (j - i + 1) * kWbfAmaxWays * sizeof(float), ctx->stream));
       i = j + 1;
     }
     WbfPackList l{};
-    for (int r : rows)
-      if (c->e[r].NP != 3) l.row[l.n++] = (unsigned char)r;
+    for (int r : which)
+      if (row(r).NP != 3) l.row[l.n++] = (unsigned char)r;
     const unsigned ny = (unsigned)l.n;
     if (one) l.n = -1;
     msk_launch_scope ls(ctx, "wbf_pack_absmax");
     // (round 4: 256 workgroups per row instead of 64 -- the eight 33 MB tensors of the 256-channel layers set this launch's time)
-    hipLaunchKernelGGL(wbf_pack_absmax_k, dim3(256, ny), dim3(256), 0, ctx->stream, c->table, l, single);
+    hipLaunchKernelGGL(wbf_pack_absmax_k, dim3(256, ny), dim3(256), 0, ctx->stream, table, l, single);
     MSK_LAUNCH_CHECK(ctx);
   }
   static const int kClasses[5][2] = {{5, 2}, {5, 3}, {3, 2}, {3, 3}, {3, 1}};
   for (const auto& kc : kClasses) {
     WbfPackList l{};
     long most = 0;
-    for (int r : rows) {
-      const WbfPackEntry& e = c->e[r];
+    for (int r : which) {
+      const WbfPackRow& e = row(r);
       if (e.K != kc[0] || e.NP != kc[1]) continue;
       l.row[l.n++] = (unsigned char)r;
       const long blocks = ((long)e.K * e.K * e.d.KC * 16 * e.d.CN + 255) / 256;
@@ -2201,7 +2212,7 @@ int pack_rows_build(msk_ctx* ctx, WbfPackCache* c, const std::vector<int>& rows)
     bool lds_ok = ctx->wbf_pack_lds != 0;
     long most_lds = 0;
     for (int i = 0; i < l.n && lds_ok; ++i) {
-      const WbfPackDesc& dd = c->e[l.row[i]].d;
+      const WbfPackDesc& dd = row(l.row[i]).d;
       lds_ok = dd.CK == dd.KC * 16 && dd.CN % 8 == 0 && dd.B % 4 == 0 && (((uintptr_t)dd.w) & 15) == 0 &&
                (dd.swap ? dd.B >= dd.CK : dd.B >= dd.CN);
       const long blocks = (long)dd.KC * (dd.CN / 8);
@@ -2213,11 +2224,11 @@ int pack_rows_build(msk_ctx* ctx, WbfPackCache* c, const std::vector<int>& rows)
       if (one) l.n = -1;
       const size_t lds = (size_t)128 * kc[0] * kc[0] * kc[0] * sizeof(float);
       msk_launch_scope ls(ctx, "wbf_pack_weights");
-      if (kc[0] == 5 && kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_lds_k<5, 2>), grid, dim3(256), lds, ctx->stream, c->table, l, single);
-      else if (kc[0] == 5) hipLaunchKernelGGL((wbf_pack_weights_lds_k<5, 3>), grid, dim3(256), lds, ctx->stream, c->table, l, single);
-      else if (kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 2>), grid, dim3(256), lds, ctx->stream, c->table, l, single);
-      else if (kc[1] == 3) hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 3>), grid, dim3(256), lds, ctx->stream, c->table, l, single);
-      else hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 1>), grid, dim3(256), lds, ctx->stream, c->table, l, single);
+      if (kc[0] == 5 && kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_lds_k<5, 2>), grid, dim3(256), lds, ctx->stream, table, l, single);
+      else if (kc[0] == 5) hipLaunchKernelGGL((wbf_pack_weights_lds_k<5, 3>), grid, dim3(256), lds, ctx->stream, table, l, single);
+      else if (kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 2>), grid, dim3(256), lds, ctx->stream, table, l, single);
+      else if (kc[1] == 3) hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 3>), grid, dim3(256), lds, ctx->stream, table, l, single);
+      else hipLaunchKernelGGL((wbf_pack_weights_lds_k<3, 1>), grid, dim3(256), lds, ctx->stream, table, l, single);
       MSK_LAUNCH_CHECK(ctx);
       continue;
     }
@@ -2225,49 +2236,16 @@ int pack_rows_build(msk_ctx* ctx, WbfPackCache* c, const std::vector<int>& rows)
     const dim3 grid((unsigned)most, (unsigned)l.n);
     if (one) l.n = -1;
     msk_launch_scope ls(ctx, "wbf_pack_weights");
-    if (kc[0] == 5 && kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_k<5, 2>), grid, dim3(256), 0, ctx->stream, c->table, l, single);
-    else if (kc[0] == 5) hipLaunchKernelGGL((wbf_pack_weights_k<5, 3>), grid, dim3(256), 0, ctx->stream, c->table, l, single);
-    else if (kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_k<3, 2>), grid, dim3(256), 0, ctx->stream, c->table, l, single);
-    else if (kc[1] == 3) hipLaunchKernelGGL((wbf_pack_weights_k<3, 3>), grid, dim3(256), 0, ctx->stream, c->table, l, single);
-    else hipLaunchKernelGGL((wbf_pack_weights_k<3, 1>), grid, dim3(256), 0, ctx->stream, c->table, l, single);
+    if (kc[0] == 5 && kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_k<5, 2>), grid, dim3(256), 0, ctx->stream, table, l, single);
+    else if (kc[0] == 5) hipLaunchKernelGGL((wbf_pack_weights_k<5, 3>), grid, dim3(256), 0, ctx->stream, table, l, single);
+    else if (kc[1] == 2) hipLaunchKernelGGL((wbf_pack_weights_k<3, 2>), grid, dim3(256), 0, ctx->stream, table, l, single);
+    else if (kc[1] == 3) hipLaunchKernelGGL((wbf_pack_weights_k<3, 3>), grid, dim3(256), 0, ctx->stream, table, l, single);
+    else hipLaunchKernelGGL((wbf_pack_weights_k<3, 1>), grid, dim3(256), 0, ctx->stream, table, l, single);
     MSK_LAUNCH_CHECK(ctx);
   }
-  for (int r : rows) c->e[r].valid = true;
+  for (int r : which)
+    if (r != kScratch) rows.e[r].valid = true;
   return 0;
-}
-
-// the row of (weights, direction, geometry), created on first use; < 0 on error
-int pack_row_lookup(msk_ctx* ctx, WbfPackCache* c, const WbfPackDesc& key, int K, int NP, size_t u_bytes) {
-  int free_row = -1, lru = -1;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r) {  // (the last row is the scratch row of uncached calls)
-    WbfPackEntry& e = c->e[r];
-    if (!e.live) {
-      if (free_row < 0) free_row = r;
-      continue;
-    }
-    const WbfPackDesc& d = e.d;
-    if (d.w == key.w && e.K == K && e.NP == NP && d.A == key.A && d.B == key.B && d.swap == key.swap && d.flip == key.flip &&
-        d.CK == key.CK && d.CN == key.CN && d.KC == key.KC && d.tsd == key.tsd && d.tsh == key.tsh && d.tsw == key.tsw) {
-      e.last_use = c->epoch;
-      return r;
-    }
-    if (lru < 0 || e.last_use < c->e[lru].last_use) lru = r;
-  }
-  if (free_row < 0) {
-    pack_row_drop(ctx, c->e[lru]);
-    free_row = lru;
-  }
-  WbfPackEntry& e = c->e[free_row];
-  e.d = key;
-  e.K = K; e.NP = NP; e.u_bytes = u_bytes;
-  if (hipMalloc((void**)&e.d.out, u_bytes) != hipSuccess) {
-    msk_fail(ctx, __FILE__, __LINE__, "pack_row_lookup", "hipMalloc failed");
-    return -1;
-  }
-  e.d.amax = c->amax + (size_t)free_row * kWbfAmaxWays;
-  e.live = true; e.valid = false; e.last_use = c->epoch;
-  hipLaunchKernelGGL(wbf_pack_desc_store_k, dim3(1), dim3(1), 0, ctx->stream, c->table + free_row, e.d);  // no pageable-memory copy
-  return free_row;
 }
 
 template <int MR, int WM, int WN, int TD, int TH, int K, int NP>
@@ -2371,7 +2349,9 @@ int run_pipeline(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int 
   char* U = nullptr;
   const float* w_amax = nullptr;
   {
-    WbfPackDesc key{};
+    WbfPackRow kr;
+    kr.K = K; kr.NP = NP;
+    WbfPackDesc& key = kr.d;
     key.w = w_canon; key.A = A; key.B = B; key.swap = swap; key.flip = g.transposed ? 1 : 0; key.CK = g.CK; key.CN = g.CN; key.KC = KC;
     key.tsd = tstr[pm[0]]; key.tsh = tstr[pm[1]]; key.tsw = tstr[pm[2]];
     key.xi_stride = (long)(u_xi / 2);
@@ -2381,23 +2361,19 @@ int run_pipeline(msk_ctx* ctx, const GConv& g, const float* w_canon, int A, int 
     const bool cached = g.w_persistent && ctx->wbf_pack_cache != 0;
     int row;
     if (cached) {
-      row = pack_row_lookup(ctx, c, key, K, NP, NXI * u_xi);
+      row = c->row_of(ctx, kr, NXI * u_xi);
       if (row < 0) return -1;
     } else {
-      // scratch row (the last one is reserved for it): rebuilt on every call, into the second workspace
-      row = WbfPackCache::kRows - 1;
-      WbfPackEntry& e = c->e[row];
+      // scratch entry: rebuilt on every call, into the second workspace
+      row = WbfPackCache::kScratch;
       key.out = (unsigned short*)msk_workspace2(ctx, NXI * u_xi);
       if (!key.out) return -1;
       key.amax = c->amax + (size_t)row * kWbfAmaxWays;
-      e.d = key; e.K = K; e.NP = NP; e.valid = false; e.live = false;
+      c->scratch = kr;
     }
-    if (!c->e[row].valid) {
-      if (pack_rows_build(ctx, c, std::vector<int>{row}) != 0) return -1;
-      if (!cached) c->e[row].valid = false;
-    }
-    U = (char*)c->e[row].d.out;
-    w_amax = c->e[row].d.amax;
+    if (!(cached && c->rows.e[row].valid) && c->build(ctx, std::vector<int>{row}) != 0) return -1;
+    U = (char*)c->row(row).d.out;
+    w_amax = c->row(row).d.amax;
   }
   // NP = 2: the source tensor is scaled into fp16 range by a power of two derived on the device from (a bound of) its
   // maximum (kept in the xform header for the weight gradient)
@@ -2655,76 +2631,3 @@ int msk_gconv_wino_bf3(msk_ctx* ctx, const GConv& g, const float* w_canon, int A
 }
 // would msk_gconv_wino_bf3 run this problem?  (launches nothing)
 bool msk_gconv_wino_bf3_accepts(msk_ctx* ctx, const GConv& g) { return wino_bf3_impl(ctx, g, nullptr, 0, 0, 0, true) == 1; }
-
-// ---- packed-weight cache: invalidation and the batched rebuild (see WbfPackCache above)
-void msk_weights_changed_impl(msk_ctx* ctx, const void* p, size_t bytes) {
-  msk_small_pack_changed(ctx, p, bytes);
-  if (!ctx->wpack || !p) return;
-  WbfPackCache* c = (WbfPackCache*)ctx->wpack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r) {
-    WbfPackEntry& e = c->e[r];
-    if (!e.live) continue;
-    const char* b0 = (const char*)e.d.w;
-    const char* b1 = b0 + (size_t)e.d.count * sizeof(float);
-    if (a0 < b1 && b0 < a1) e.valid = false;
-  }
-}
-void msk_weights_freed_impl(msk_ctx* ctx, const void* p, size_t bytes) {
-  // msk_free: every row whose weights lie (even partly) inside the freed allocation [p, p + bytes) is DROPPED -- a row that
-  // was only invalidated would be rebuilt by the next optimizer call (msk_wbf_prepack_impl) from freed memory, and its
-  // packed buffer would stay allocated until the LRU evicts it.  bytes == 0 (range unknown): the rows that begin at p.
-  msk_small_pack_freed(ctx, p, bytes);
-  if (!ctx->wpack || !p) return;
-  WbfPackCache* c = (WbfPackCache*)ctx->wpack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r) {
-    WbfPackEntry& e = c->e[r];
-    if (!e.live) continue;
-    const char* b0 = (const char*)e.d.w;
-    const char* b1 = b0 + (size_t)e.d.count * sizeof(float);
-    if (bytes ? (a0 < b1 && b0 < a1) : b0 == a0) pack_row_drop(ctx, e);
-  }
-}
-int msk_wbf_prepack_impl(msk_ctx* ctx) {
-  if (ctx->wbf_prepack && msk_small_prepack(ctx, nullptr, 0) != 0) return -1;
-  if (!ctx->wpack || !ctx->wbf_prepack) return 0;
-  WbfPackCache* c = (WbfPackCache*)ctx->wpack;
-  std::vector<int> rows;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r) {
-    const WbfPackEntry& e = c->e[r];
-    if (e.live && !e.valid && e.last_use >= c->epoch - 1) rows.push_back(r);  // rows used since the previous rebuild
-  }
-  c->epoch += 1;
-  return pack_rows_build(ctx, c, rows);
-}
-// the rows whose weights lie inside [p, p + bytes) only, on the CURRENT stream; the use epoch does not advance
-// (msk_sgd_momentum_eager: one call per block of the model, msk_wbf_prepack_impl closes the step)
-int msk_wbf_prepack_range_impl(msk_ctx* ctx, const void* p, size_t bytes) {
-  if (ctx->wbf_prepack && p && msk_small_prepack(ctx, p, bytes) != 0) return -1;
-  if (!ctx->wpack || !ctx->wbf_prepack || !p) return 0;
-  WbfPackCache* c = (WbfPackCache*)ctx->wpack;
-  const char* a0 = (const char*)p;
-  const char* a1 = a0 + bytes;
-  std::vector<int> rows;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r) {
-    const WbfPackEntry& e = c->e[r];
-    if (!e.live || e.valid || e.last_use < c->epoch - 1) continue;
-    const char* b0 = (const char*)e.d.w;
-    const char* b1 = b0 + (size_t)e.d.count * sizeof(float);
-    if (b0 >= a0 && b1 <= a1) rows.push_back(r);   // wholly inside: a row that straddles the slice waits for the full rebuild
-  }
-  return pack_rows_build(ctx, c, rows);
-}
-void msk_wbf_pack_cache_free(msk_ctx* ctx) {
-  if (!ctx->wpack) return;
-  WbfPackCache* c = (WbfPackCache*)ctx->wpack;
-  for (int r = 0; r < WbfPackCache::kRows - 1; ++r)
-    if (c->e[r].live && c->e[r].d.out) hipFree(c->e[r].d.out);
-  if (c->table) hipFree(c->table);
-  if (c->amax) hipFree(c->amax);
-  delete c;
-  ctx->wpack = nullptr;
-}

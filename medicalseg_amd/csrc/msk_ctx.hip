@@ -110,6 +110,28 @@ int msk_join_side_impl(msk_ctx* ctx) {
   return 0;
 }
 
+// ---- the weight hooks: both packed-weight caches of the context (msk_pack.h), the small one first
+void msk_weights_changed_impl(msk_ctx* ctx, const void* p, size_t bytes) {
+  for (msk_pack_cache* c : {ctx->spack, ctx->wpack})
+    if (c && p) c->changed(p, bytes);
+}
+// msk_free: every row whose weights lie (even partly) inside the freed allocation [p, p + bytes) is dropped;
+// bytes == 0 (range unknown): the rows that begin at p
+void msk_weights_freed_impl(msk_ctx* ctx, const void* p, size_t bytes) {
+  for (msk_pack_cache* c : {ctx->spack, ctx->wpack})
+    if (c && p) c->freed(ctx, p, bytes);
+}
+static int prepack(msk_ctx* ctx, const void* p, size_t bytes) {
+  if (!ctx->wbf_prepack) return 0;
+  for (msk_pack_cache* c : {ctx->spack, ctx->wpack})
+    if (c && c->prepack(ctx, p, bytes) != 0) return -1;
+  return 0;
+}
+int msk_prepack_impl(msk_ctx* ctx) { return prepack(ctx, nullptr, 0); }
+// the rows whose weights lie inside [p, p + bytes) only, on the CURRENT stream; the use epoch does not advance
+// (msk_sgd_momentum_eager: one call per block of the model, msk_prepack_impl closes the step)
+int msk_prepack_range_impl(msk_ctx* ctx, const void* p, size_t bytes) { return p ? prepack(ctx, p, bytes) : 0; }
+
 extern "C" {
 
 int msk_version(void) { return 100; }
@@ -189,8 +211,8 @@ int msk_ctx_destroy(msk_ctx* ctx) {
   for (auto e : ctx->event_pool) hipEventDestroy(e);
   for (auto e : ctx->marks) if (e) hipEventDestroy(e);
   if (ctx->ev_xctx) hipEventDestroy(ctx->ev_xctx);
-  msk_wbf_pack_cache_free(ctx);
-  msk_small_pack_free(ctx);
+  delete ctx->wpack;
+  delete ctx->spack;
   if (ctx->ws) hipFree(ctx->ws);
   if (ctx->ws2) hipFree(ctx->ws2);
   if (ctx->ws3) hipFree(ctx->ws3);

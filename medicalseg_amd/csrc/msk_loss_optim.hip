@@ -707,20 +707,20 @@ int msk_sgd_momentum(msk_ctx* ctx, float* param, const float* grad, float* veloc
     if (sgd_launch(ctx, param, grad, velocity, lo, lr, momentum, weight_decay, grad_scale) != 0) return -1;
     if (sgd_launch(ctx, param + hi, grad + hi, velocity + hi, count - hi, lr, momentum, weight_decay, grad_scale) != 0) return -1;
     msk_weights_changed_impl(ctx, param, count * sizeof(float));
-    if (msk_wbf_prepack_impl(ctx) != 0) return -1;
+    if (msk_prepack_impl(ctx) != 0) return -1;
     if (msk_join_side_impl(ctx) != 0) return -1;
     if (sgd_launch(ctx, param + lo, grad + lo, velocity + lo, hi - lo, lr, momentum, weight_decay, grad_scale) != 0) return -1;
     // the late slice changes AFTER the re-pack above: a packed row over it (none today -- the late tensor is in_tr.conv1, one
     // input channel, which never enters the pack cache) must not be left marked valid (advisor, round 4)
     msk_weights_changed_impl(ctx, param + lo, (hi - lo) * sizeof(float));
-    return msk_wbf_prepack_range_impl(ctx, param + lo, (hi - lo) * sizeof(float));
+    return msk_prepack_range_impl(ctx, param + lo, (hi - lo) * sizeof(float));
   }
   if (msk_join_side_impl(ctx) != 0) return -1;  // weight gradients may still be running on the side stream
   if (sgd_launch(ctx, param, grad, velocity, count, lr, momentum, weight_decay, grad_scale) != 0) return -1;
   // the packed / transformed forms of the convolution weights inside [param, param + count) are stale now: rebuild the ones
   // in use in one go (two launches instead of one pack + one maximum per layer and direction inside the next step)
   msk_weights_changed_impl(ctx, param, count * sizeof(float));
-  return msk_wbf_prepack_impl(ctx);
+  return msk_prepack_impl(ctx);
 }
 
 // Eager update of ONE slice of the arena (round 5; round-4 "measured but not built (i)"): everything that produces the
@@ -753,7 +753,7 @@ int msk_sgd_momentum_eager(msk_ctx* ctx, float* param, const float* grad, float*
       if (sgd_launch(ctx, param, grad, velocity, lo, lr, momentum, weight_decay, grad_scale) != 0) return -1;
       if (sgd_launch(ctx, param + hi, grad + hi, velocity + hi, count - hi, lr, momentum, weight_decay, grad_scale) != 0) return -1;
       msk_weights_changed_impl(ctx, param, count * sizeof(float));
-      if (msk_wbf_prepack_range_impl(ctx, param, count * sizeof(float)) != 0) return -1;
+      if (msk_prepack_range_impl(ctx, param, count * sizeof(float)) != 0) return -1;
       if (inside) {
         ctx->late_piece.param = param + lo; ctx->late_piece.grad = grad + lo; ctx->late_piece.velocity = velocity + lo;
         ctx->late_piece.count = hi - lo;
@@ -767,7 +767,7 @@ int msk_sgd_momentum_eager(msk_ctx* ctx, float* param, const float* grad, float*
     msk_side_scope side(ctx);   // (no side stream: the same launches on the calling stream, in order)
     if (sgd_launch(ctx, param, grad, velocity, count, lr, momentum, weight_decay, grad_scale) != 0) return -1;
     msk_weights_changed_impl(ctx, param, count * sizeof(float));
-    if (msk_wbf_prepack_range_impl(ctx, param, count * sizeof(float)) != 0) return -1;
+    if (msk_prepack_range_impl(ctx, param, count * sizeof(float)) != 0) return -1;
   }
   return 0;
 }
@@ -782,7 +782,7 @@ int msk_sgd_momentum_finish(msk_ctx* ctx) {
     if (sgd_launch(ctx, lp.param, lp.grad, lp.velocity, lp.count, lp.lr, lp.momentum, lp.weight_decay, lp.grad_scale) != 0) return -1;
     msk_weights_changed_impl(ctx, lp.param, lp.count * sizeof(float));
   }
-  return msk_wbf_prepack_impl(ctx);
+  return msk_prepack_impl(ctx);
 }
 
 // one launch of adam_k under `tag`; count >= 1 (every caller returns earlier on 0)
@@ -813,7 +813,7 @@ int msk_adam(msk_ctx* ctx, float* param, const float* grad, float* moment1, floa
   if (adam_launch(ctx, "adam", param, grad, moment1, moment2, count, lr_t, beta1, beta2, eps_t, weight_decay, grad_scale, nullptr,
                   -INFINITY, INFINITY) != 0) return -1;
   msk_weights_changed_impl(ctx, param, count * sizeof(float));
-  return msk_wbf_prepack_impl(ctx);
+  return msk_prepack_impl(ctx);
 }
 
 int msk_sgd_momentum_clip(msk_ctx* ctx, float* param, const float* grad, float* velocity, size_t count, float lr, float momentum,
@@ -831,7 +831,7 @@ int msk_sgd_momentum_clip(msk_ctx* ctx, float* param, const float* grad, float* 
                     clip_rec, clip_min, clip_max) != 0) return -1;
   // the packed / transformed forms of the convolution weights inside [param, param + count) are stale now (msk_sgd_momentum)
   msk_weights_changed_impl(ctx, param, count * sizeof(float));
-  return msk_wbf_prepack_impl(ctx);
+  return msk_prepack_impl(ctx);
 }
 
 int msk_adam_clip(msk_ctx* ctx, float* param, const float* grad, float* moment1, float* moment2, size_t count, float lr,
@@ -850,7 +850,7 @@ int msk_adam_clip(msk_ctx* ctx, float* param, const float* grad, float* moment1,
   if (adam_launch(ctx, "adam_clip", param, grad, moment1, moment2, count, lr_t, beta1, beta2, eps_t, weight_decay, grad_scale,
                   clip_rec, clip_min, clip_max) != 0) return -1;
   msk_weights_changed_impl(ctx, param, count * sizeof(float));
-  return msk_wbf_prepack_impl(ctx);
+  return msk_prepack_impl(ctx);
 }
 
 }  // extern "C"

@@ -235,6 +235,58 @@ def test_eager_optimizer_is_bitwise_the_plain_order(shape):
     assert np.abs(vela).max() > 0
 
 
+# call counts of the weight-pack and absmax launches in the third training step of the 16^3 VNet below, as measured
+# at commit 1a969f7 (deterministic: the comparison is exact)
+PACK_LAUNCHES_STEP3 = {
+    False: {"absmax": 10, "pack_weights_batch": 1, "pack_weights_foldn": 1, "pack_weights_tightk": 1, "pack_weights_wino": 4,
+            "wbf_pack_absmax": 1, "wbf_pack_weights": 1},
+    True: {"absmax": 10, "pack_weights_batch": 9, "pack_weights_foldn": 1, "pack_weights_tightk": 1, "pack_weights_wino": 4,
+           "wbf_pack_absmax": 2, "wbf_pack_weights": 2},
+}
+
+
+@pytest.mark.parametrize("eager", [False, True])
+def test_training_step_pack_launches_do_not_move(eager):
+    """Where the packed weights are rebuilt is part of the step's launch plan: in steady state the optimizer kernels rebuild
+    every row in use in batched launches and no convolution packs for itself.  Pins the call counts of every pack_weights*,
+    wbf_pack_* and absmax* tag of the third step, for the plain and the eager optimizer order."""
+    from medicalseg_amd import nn
+    from medicalseg_amd import optimizer as optim
+    from medicalseg_amd.models import CrossEntropyLoss, DiceLoss, MixedLoss
+    from medicalseg_amd.utils import loss_computation
+    ncls, K, S, N, shape = 3, ((2, 2, 2),) * 4, ((2, 2, 2),) * 4, 2, (16, 16, 16)
+    rng = np.random.default_rng(5)
+    nn.Dropout3D._site_counter = 0
+    model, _ = _build(ncls, K, S, seed=6)
+    opt = optim.Momentum(1e-2, parameters=model.parameters(), momentum=0.9, weight_decay=1e-4)
+    if eager:
+        assert opt.enable_eager(model) is True
+        opt.eager_min_floats = 0
+    losses = {"types": [MixedLoss([CrossEntropyLoss(), DiceLoss()], [1, 1])], "coef": [1]}
+    model.train()
+    model.set_dropout_masks(None)
+    nn.Dropout3D.step, nn.Dropout3D.seed = 0, 3
+    d = dev()
+    d.prof_reset()
+    d.prof_enable(True)
+    try:
+        for step in range(3):
+            if step == 2:
+                d.prof_reset()
+            x = rng.standard_normal((N, 1) + shape).astype(np.float32)
+            y = rng.integers(0, ncls, (N,) + shape).astype(np.int32)
+            loss_list, _ = loss_computation(model(x), to_labels(y), losses)
+            sum(loss_list).backward()
+            opt.step()
+            model.clear_gradients()
+        d.sync()
+    finally:
+        d.prof_enable(False)
+    got = {t: c for t, (c, _) in d.prof_report().items() if t.startswith(("pack_weights", "wbf_pack_", "absmax"))}
+    print("\npack launches of step 3, eager %s: %r" % (eager, dict(sorted(got.items()))))
+    assert got == PACK_LAUNCHES_STEP3[eager]
+
+
 def test_late_weight_gradient_does_not_see_the_updated_prelu_slopes():
     """Advisor, round 5: in_tr.conv1's weight gradient (the LAST kernel of the side stream) evaluates PReLU backward from the
     slopes of in_tr.relu1 -- a tensor of the parameter arena that the optimizer updates behind ev_late while that kernel is

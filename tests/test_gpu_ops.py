@@ -1339,6 +1339,43 @@ def test_small_pack_cache_follows_every_weight_write():
             d.set_option("small_pack_cache", 1)
 
 
+def test_small_pack_cache_evicts_and_keeps_following_writes():
+    """More live weight tensors than the cache has rows (128): 130 distinct 1x1x1 weight tensors, one forward call each, every
+    result against the float64 oracle; then the first tensor again (the sweep has evicted rows by then; in a fresh process the
+    first tensor's is among them), then an early tensor overwritten with h2d: no call may see another tensor's image or a
+    stale one."""
+    d = dev()
+    rng = np.random.default_rng(23)
+    f8 = lambda a: a.astype(np.float64)
+    cin = cout = 20
+    k = s_ = (1, 1, 1)
+    p = (0, 0, 0)
+    N, D, H, W = 1, 8, 16, 16
+    x = rng.standard_normal((N, cin, D, H, W)).astype(np.float32)
+    xt, yt = t_from_ncdhw(x), t_empty(N, cout, D, H, W)
+    cd = _desc(k, s_, p)
+    b = np.zeros(cout, np.float32)
+    bp = vec(b)
+    tol = 8e-6 * np.sqrt(cin / 1000 + 1)
+    mkw = lambda sc: (rng.standard_normal((cout, cin) + k) * sc / np.sqrt(cin)).astype(np.float32)
+
+    def check(wp, w, what):
+        d.call("msk_conv3d_fwd", cd, xt.msk(), vp(wp), vp(bp), yt.msk())
+        e = rel_err(t_to_ncdhw(yt), O.conv3d(f8(x), f8(w), f8(b), s_, p))
+        assert e < tol, (what, e)
+
+    ws = [mkw(1.0 + i) for i in range(130)]          # distinct scales: another tensor's image is far outside the tolerance
+    wps = [vec(w.ravel()) for w in ws]
+    for i, (wp, w) in enumerate(zip(wps, ws)):
+        check(wp, w, ("sweep", i))
+    check(wps[0], ws[0], "the first tensor again, after the sweep's evictions")
+    w_new = mkw(0.25)
+    d.h2d(wps[3], w_new.ravel())
+    check(wps[3], w_new, "an early tensor after h2d")
+    for wp in wps:
+        dfree(wp)
+
+
 @pytest.mark.parametrize("cin,cout,src", [(64, 16, (2, 8, 8, 8)), (32, 8, (1, 5, 6, 7)), (64, 16, (1, 16, 16, 16)),
                                           (64, 16, (1, 2, 4, 32)), (32, 8, (2, 2, 3, 64)), (96, 16, (1, 2, 2, 32))])   # the last three: the LDS-staged form (W % 32 == 0)
 def test_convT_bwd_bnact_equals_the_three_call_form(cin, cout, src):

@@ -759,6 +759,53 @@ def test_wbf_packed_weight_cache_follows_every_weight_write():
         d.set_option("wbf_pack_cache", 1)
 
 
+def test_wbf_packed_weight_cache_evicts_and_keeps_following_writes():
+    """More live weight tensors than the cache has rows (249): 251 distinct 5^3 weight tensors, disjoint slices of one
+    allocation, one forward call each.  The first, the middle and the last result against the float64 oracle; tensors 0 and 1
+    again after the sweep (it has evicted rows by then; in a fresh process tensor 0's is among them): bitwise their first results; then an optimizer update of
+    tensor 0's slice, which must reach the next call."""
+    cin = cout = 32
+    N, D, H, W = 1, 16, 16, 8
+    k, s_, p = (5, 5, 5), (1, 1, 1), (2, 2, 2)
+    nt = 251
+    d = dev()
+    d.set_option("conv_split", 2)
+    rng = np.random.default_rng(17)
+    x = rng.standard_normal((N, cin, D, H, W)).astype(np.float32)
+    xt, yt = t_from_ncdhw(x), t_empty(N, cout, D, H, W)
+    cd = _desc(k, s_, p)
+    f8 = lambda a: a.astype(np.float64)
+    b = np.zeros(cout, np.float32)
+    bp = vec(b)
+    count = cout * cin * 125                        # 512000 bytes per tensor: every slice keeps the allocation's alignment
+    ws = rng.standard_normal((nt, cout, cin) + k, dtype=np.float32) / np.float32(np.sqrt(cin * 125))
+    ws *= (1.0 + np.arange(nt, dtype=np.float32) % 7).reshape(nt, 1, 1, 1, 1, 1)   # neighbours differ in their maximum as well
+    arena = dmalloc(nt * count * 4)
+    d.h2d(arena, ws.ravel())
+    wp = lambda i: arena + i * count * 4
+
+    def run(i):
+        d.call("msk_conv3d_fwd", cd, xt.msk(), vp(wp(i)), vp(bp), yt.msk())
+        return t_to_ncdhw(yt)
+
+    first = [run(i) for i in range(nt)]
+    for i in (0, nt // 2, nt - 1):
+        e = rel_err(first[i], O.conv3d(f8(x), f8(ws[i]), f8(b), s_, p))
+        assert e < _conv_tol(cin * 125), (i, e)
+    for i in (0, 1):
+        assert np.array_equal(run(i), first[i]), i
+    g = (rng.standard_normal((cout, cin) + k) / np.sqrt(cin * 125)).astype(np.float32)
+    gp, vel = vec(g.ravel()), vec(np.zeros(count, np.float32))
+    d.call("msk_sgd_momentum", vp(wp(0)), vp(gp), vp(vel), C.c_size_t(count), C.c_float(0.5), C.c_float(0.0), C.c_float(0.0),
+           C.c_float(1.0))
+    w_new = d.d2h(wp(0), (cout, cin) + k, np.float32)
+    np.testing.assert_allclose(w_new, ws[0] - 0.5 * g, rtol=0, atol=4e-7 * np.abs(ws[0]).max())   # a few fp32 roundings (6e-8 each) of values up to 1.5 max|w|, on either side
+    e = rel_err(run(0), O.conv3d(f8(x), f8(ws[0]) - 0.5 * f8(g), f8(b), s_, p))
+    assert e < _conv_tol(cin * 125), ("after sgd", e)
+    assert np.array_equal(run(1), first[1])         # the neighbouring slice is untouched
+    dfree(arena)
+
+
 def test_wbf_packed_weight_cache_free_of_an_arena_and_foreign_writes():
     """Round-3 advisor: (a) a weight tensor that lives INSIDE a larger allocation (the parameter arena) -- msk_free of the arena
     must drop its cache row, not just invalidate it: the next optimizer call rebuilds every stale row in use and would read
