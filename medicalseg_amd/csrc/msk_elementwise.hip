@@ -1208,16 +1208,6 @@ affine_act_bwd_apply_d12_k(const float* __restrict__ x, const float* __restrict_
   if (dx_amax) block_atomic_max(dx_amax, mx);
 }
 
-// is every (non-null) tensor of a pass dense, 16-byte aligned, with a channel count that divides 12?
-inline bool d12_ok(const msk_tensor& t) { return t.p == nullptr || (t.ld == t.c && (((uintptr_t)t.p) % 16 == 0)); }
-inline bool d12_shape(const msk_tensor& x, long voxels) {
-  return (x.c == 1 || x.c == 2 || x.c == 3 || x.c == 6) && (voxels * x.c) % 12 == 0;
-}
-int g_dense12 = 1;   // option "dense12": 0 = the scalar kernels (A/B)
-
-inline bool vec4_ok(const msk_tensor& t) {
-  return t.p == nullptr || ((t.c % 4 == 0) && (t.ld % 4 == 0) && (((uintptr_t)t.p) % 16 == 0));
-}
 }  // namespace
 
 extern "C" {
@@ -1246,24 +1236,129 @@ __global__ void noop_k() {}
 inline void noop_launches(msk_ctx* ctx) {
   for (int i = 0; i < ctx->noop_after_merge; ++i) hipLaunchKernelGGL(noop_k, dim3(1), dim3(64), 0, ctx->stream);
 }
-}  // namespace
 
-int msk_bn_stats_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* stats, const msk_bn_fin* fin) {
+// ---------------------------------------------------------------------------
+// Which form of a pass runs.  Every entry point below asks ew_select (the element-wise passes) or reduce_plan (the
+// block-partitioned reductions); no eligibility test is written anywhere else.
+//
+// A pass has x, up to three more tensors of x's shape (out | dout, dx, dres; a null one passes every test) and a residual that
+// is null, a broadcast one of fewer channels (read with scalar loads in every form that takes it) or one of x's channel count.
+//   pass_v4   every tensor float4-addressable (C % 4 == 0, ld % 4 == 0, 16-byte aligned), the residual too when it is full
+//   pass_d12  option "dense12", C in {1, 2, 3, 6} with voxels * C % 12 == 0, every tensor dense (ld == c) and 16-byte aligned,
+//             the residual null or full
+// Element-wise passes try  D12 (only if !pass_v4 and the call does not rule it out), CS (pass_v4 and C / 4 a power of two
+// <= 256: a lane keeps its channel quad), K4 (pass_v4), K1.
+// Reductions try           V4 (pass_v4 and C / 4 <= 256), D12, SCALAR.
+// The element-wise order puts D12 first and the reductions' order puts the float4 form first, and both select the same forms:
+// pass_d12 needs a channel count that divides 12 without being a multiple of 4 and pass_v4 needs a multiple of 4, so at most one
+// of the two holds for any x and the order between them cannot matter ("!pass_v4" in front of D12 is implied by d12_shape).  For
+// one set of tensors D12 <-> D12, CS / K4 <-> V4 and K1 <-> SCALAR, except that more than 1024 channels are K4 but SCALAR.
+// tests/test_gpu_elementwise_forms.py mirrors exactly this block (_elementwise_form, _reduce_form, _copy_form).
+// ---------------------------------------------------------------------------
+inline bool vec4_ok(const msk_tensor& t) {
+  return t.p == nullptr || ((t.c % 4 == 0) && (t.ld % 4 == 0) && (((uintptr_t)t.p) % 16 == 0));
+}
+inline bool d12_ok(const msk_tensor& t) { return t.p == nullptr || (t.ld == t.c && (((uintptr_t)t.p) % 16 == 0)); }
+inline bool d12_shape(const msk_tensor& x, long voxels) {
+  return (x.c == 1 || x.c == 2 || x.c == 3 || x.c == 6) && (voxels * x.c) % 12 == 0;
+}
+int g_dense12 = 1;   // option "dense12": 0 = the scalar kernels (A/B)
+
+struct PassTensors {
+  msk_tensor x, res, o1, o2, o3;   // x, the residual, the other full-size tensors
+};
+inline bool pass_v4(const PassTensors& t) {
+  return vec4_ok(t.x) && vec4_ok(t.o1) && vec4_ok(t.o2) && vec4_ok(t.o3) && (t.res.p == nullptr || t.res.c != t.x.c || vec4_ok(t.res));
+}
+inline bool pass_d12(const PassTensors& t, long voxels) {
+  return g_dense12 && d12_shape(t.x, voxels) && d12_ok(t.x) && d12_ok(t.o1) && d12_ok(t.o2) && d12_ok(t.o3) &&
+         (t.res.p == nullptr || (t.res.c == t.x.c && d12_ok(t.res)));
+}
+
+enum class EwForm { D12, CS, K4, K1 };
+struct EwSel {
+  EwForm form;
+  int cshift;   // CS: log2(C / 4)
+};
+inline EwSel ew_select(const PassTensors& t, long voxels, bool no_d12) {
+  if (!pass_v4(t)) return {!no_d12 && pass_d12(t, voxels) ? EwForm::D12 : EwForm::K1, 0};
+  const int cq = t.x.c / 4;
+  if (cq < 1 || (cq & (cq - 1)) != 0 || cq > kThreads) return {EwForm::K4, 0};
+  int cshift = 0;
+  while ((1 << cshift) < cq) ++cshift;
+  return {EwForm::CS, cshift};
+}
+
+// A block-partitioned reduction: nb workgroups (x cblocks channel blocks in the SCALAR form) of `rows` voxel rows, `lanes` lanes
+// per row; each leaves one record of `stride` floats per quantity, which the merge kernels sum in a fixed order.  nb, stride and
+// the workspace layout decide that order and with it the bits of the sums.
+enum class RedForm { V4, D12, SCALAR };
+struct ReducePlan {
+  RedForm form;
+  int nb;
+  int lanes;     // V4: pow2ceil(C / 4) quad lanes; D12, SCALAR: chan_geom's CB
+  int rows;      // kThreads / lanes: V4's VL, chan_geom's VPB
+  int stride;    // V4: 4 * lanes; D12, SCALAR: CB
+  int cblocks;   // chan_geom's channel blocks; 1 for V4 (and for D12, whose C <= 6)
+  size_t bytes(int nq) const { return (size_t)cblocks * nb * nq * stride * sizeof(float); }
+};
+// site: the "reduce_vpl_site" index (0 statistics, 1 BatchNorm backward sums, 2 joins, 3 channel sums); has_v4: the pass has a float4 kernel
+inline ReducePlan reduce_plan(const PassTensors& t, long voxels, int num_cu, int site, bool has_v4 = true) {
+  ReducePlan p;
+  if (has_v4 && t.x.c % 4 == 0 && t.x.c / 4 <= kThreads && pass_v4(t)) {
+    p.form = RedForm::V4;
+    p.lanes = pow2ceil(t.x.c / 4);
+    p.stride = 4 * p.lanes;
+    p.cblocks = 1;
+  } else {
+    const ChanGeom g = chan_geom(t.x.c);
+    p.form = pass_d12(t, voxels) ? RedForm::D12 : RedForm::SCALAR;
+    p.lanes = p.stride = g.CB;
+    p.cblocks = g.cblocks;
+  }
+  p.rows = kThreads / p.lanes;
+  p.nb = reduce_blocks(voxels, p.rows, num_cu, site);
+  return p;
+}
+
+// The dense-12 kernels exist for the channel counts d12_shape admits: launch(std::integral_constant<int, C>)
+template <class Launch>
+inline void d12_ladder(int C, Launch&& launch) {
+  if (C == 1) launch(std::integral_constant<int, 1>{});
+  else if (C == 2) launch(std::integral_constant<int, 2>{});
+  else if (C == 3) launch(std::integral_constant<int, 3>{});
+  else launch(std::integral_constant<int, 6>{});
+}
+
+// The second launch of every reduction: nb records of `stride` floats per quantity -> per-channel results.
+// fin (nullable): + msk_bn_finalize(world 1) in the same launch
+int stats_merge_tail(msk_ctx* ctx, const float* partial, int nb, int C, int stride, float* stats, const msk_bn_fin* fin) {
   msk_launch_scope ls(ctx, "bn_stats_merge");
-  hipLaunchKernelGGL(bn_stats_merge, dim3(C), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, C, C, stats, fin ? *fin : msk_bn_fin{});
+  hipLaunchKernelGGL(bn_stats_merge, dim3(C), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, C, stride, stats, fin ? *fin : msk_bn_fin{});
   MSK_LAUNCH_CHECK(ctx);
   noop_launches(ctx);
   return 0;
 }
-
-int msk_join_sums_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* unit_sums, float* u_dbeta, float* u_dgamma,
-                        float* u_dalpha, float* dalpha) {
+// quantity q of channel c -> sums[q * C + c] (added to it with `accumulate`) and, where gq is not null, added to gq[c]
+int sums_merge_tail(msk_ctx* ctx, const float* partial, int nb, int C, int stride, int nq, float* sums, int accumulate,
+                    float* g0 = nullptr, float* g1 = nullptr, float* g2 = nullptr, float* g3 = nullptr) {
   msk_launch_scope ls(ctx, "sums_merge");
-  hipLaunchKernelGGL(sums_merge_k, dim3(4 * C), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, C, 4 * pow2ceil(C / 4), 4, unit_sums, 0,
-                     u_dbeta, u_dgamma, u_dalpha, dalpha);
+  hipLaunchKernelGGL(sums_merge_k, dim3(nq * C), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, C, stride, nq, sums, accumulate,
+                     g0, g1, g2, g3);
   MSK_LAUNCH_CHECK(ctx);
   noop_launches(ctx);
   return 0;
+}
+}  // namespace
+
+// the merges of the partial records that convolution epilogues leave: one record of C floats per workgroup ...
+int msk_bn_stats_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* stats, const msk_bn_fin* fin) {
+  return stats_merge_tail(ctx, partial, nb, C, C, stats, fin);
+}
+// ... and the four quantities of a join in the V4 layout
+int msk_join_sums_merge(msk_ctx* ctx, const float* partial, int nb, int C, float* unit_sums, float* u_dbeta, float* u_dgamma,
+                        float* u_dalpha, float* dalpha) {
+  return sums_merge_tail(ctx, partial, nb, C, 4 * pow2ceil(C / 4), 4, unit_sums, 0, u_dbeta, u_dgamma, u_dalpha, dalpha);
 }
 
 extern "C" {
@@ -1273,59 +1368,27 @@ int msk_bn_stats(msk_ctx* ctx, msk_tensor x, float* stats_local) { return msk_bn
 int msk_bn_stats_fin(msk_ctx* ctx, msk_tensor x, float* stats_local, const msk_bn_fin* fin) {
   const long voxels = msk_voxels(x);
   MSK_REQUIRE(ctx, voxels > 0 && x.c > 0, "empty tensor");
-  if (x.c % 4 == 0 && x.c / 4 <= kThreads && vec4_ok(x)) {
-    const int QCB = pow2ceil(x.c / 4), VL = kThreads / QCB;
-    const int nb = reduce_blocks(voxels, VL, ctx->num_cu, 0);
-    float* partial = (float*)msk_workspace(ctx, (size_t)nb * 4 * QCB * 3 * sizeof(float));
-    if (!partial) return -1;
-    {
-      msk_launch_scope ls(ctx, "bn_stats_partial");
-      hipLaunchKernelGGL(bn_stats_partial_v4, dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p, voxels, x.c,
-                         x.ld, QCB, VL, partial);
-      MSK_LAUNCH_CHECK(ctx);
-    }
-    msk_launch_scope ls(ctx, "bn_stats_merge");
-    hipLaunchKernelGGL(bn_stats_merge, dim3(x.c), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, x.c, 4 * QCB, stats_local,
-                       fin ? *fin : msk_bn_fin{});
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
-  }
-  ChanGeom g = chan_geom(x.c);
-  int nb = reduce_blocks(voxels, g.VPB, ctx->num_cu, 0);
-  size_t bytes = (size_t)g.cblocks * nb * g.CB * 3 * sizeof(float);
-  float* partial = (float*)msk_workspace(ctx, bytes);
+  const ReducePlan p = reduce_plan(PassTensors{x}, voxels, ctx->num_cu, 0);
+  float* partial = (float*)msk_workspace(ctx, p.bytes(3));
   if (!partial) return -1;
-  if (g_dense12 && d12_shape(x, voxels) && d12_ok(x)) {
-    const long groups = voxels * x.c / 12;
-    {
-      msk_launch_scope ls(ctx, "bn_stats_partial");
-#define D12_ST(C_) hipLaunchKernelGGL(bn_stats_partial_d12_k<C_>, dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p, groups, g.CB, partial)
-      if (x.c == 1) D12_ST(1); else if (x.c == 2) D12_ST(2); else if (x.c == 3) D12_ST(3); else D12_ST(6);
-#undef D12_ST
-      MSK_LAUNCH_CHECK(ctx);
-    }
-    msk_launch_scope ls(ctx, "bn_stats_merge");
-    hipLaunchKernelGGL(bn_stats_merge, dim3(x.c), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, x.c, g.CB, stats_local,
-                       fin ? *fin : msk_bn_fin{});
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
-  }
   {
     msk_launch_scope ls(ctx, "bn_stats_partial");
-    hipLaunchKernelGGL(bn_stats_partial, dim3(nb, g.cblocks), dim3(kThreads), 0, ctx->stream,
-                       (const float*)x.p, voxels, x.c, x.ld, g.CB, g.VPB, partial);
+    if (p.form == RedForm::V4) {
+      hipLaunchKernelGGL(bn_stats_partial_v4, dim3(p.nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p, voxels, x.c,
+                         x.ld, p.lanes, p.rows, partial);
+    } else if (p.form == RedForm::D12) {
+      const long groups = voxels * x.c / 12;
+      d12_ladder(x.c, [&](auto c) {
+        hipLaunchKernelGGL(bn_stats_partial_d12_k<decltype(c)::value>, dim3(p.nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p,
+                           groups, p.stride, partial);
+      });
+    } else {
+      hipLaunchKernelGGL(bn_stats_partial, dim3(p.nb, p.cblocks), dim3(kThreads), 0, ctx->stream,
+                         (const float*)x.p, voxels, x.c, x.ld, p.lanes, p.rows, partial);
+    }
     MSK_LAUNCH_CHECK(ctx);
   }
-  {
-    msk_launch_scope ls(ctx, "bn_stats_merge");
-    hipLaunchKernelGGL(bn_stats_merge, dim3(x.c), dim3(merge_threads(nb)), 0, ctx->stream, partial, nb, x.c, g.CB, stats_local,
-                       fin ? *fin : msk_bn_fin{});
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-  }
-  return 0;
+  return stats_merge_tail(ctx, partial, p.nb, x.c, p.stride, stats_local, fin);
 }
 
 int msk_bn_finalize(msk_ctx* ctx, const float* gathered, int world, double count_per_rank, int C,
@@ -1357,30 +1420,22 @@ static int affine_act_fwd_impl(msk_ctx* ctx, msk_tensor x, const float* scale, c
   MSK_REQUIRE(ctx, (scale == nullptr) == (shift == nullptr), "scale and shift go together");
   if (res.p) MSK_REQUIRE(ctx, res.c > 0 && (res.c == x.c || x.c % res.c == 0), "residual channels must tile");
   const long voxels = msk_voxels(x);
-  const bool v4 = vec4_ok(x) && vec4_ok(out) && (res.p == nullptr || res.c != x.c || vec4_ok(res));
+  const EwSel sel = ew_select(PassTensors{x, res, out}, voxels, alpha_in || out2.p);
   msk_launch_scope ls(ctx, "affine_act_fwd");
-  const int cq = x.c / 4;
-  if (g_dense12 && !v4 && !alpha_in && !out2.p && d12_shape(x, voxels) && d12_ok(x) && d12_ok(out) && (res.p == nullptr || (res.c == x.c && d12_ok(res)))) {
-    const long groups = voxels * x.c / 12;
-    const dim3 grid(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap));
-#define D12_FWD(C_) hipLaunchKernelGGL(affine_act_fwd_d12_k<C_>, grid, dim3(kThreads), 0, ctx->stream, (const float*)x.p, scale, shift, \
-                                       (const float*)res.p, alpha, (float*)out.p, groups, (unsigned*)out_amax)
-    if (x.c == 1) D12_FWD(1); else if (x.c == 2) D12_FWD(2); else if (x.c == 3) D12_FWD(3); else D12_FWD(6);
-#undef D12_FWD
-    MSK_LAUNCH_CHECK(ctx);
-    return 0;
-  }
-  if (v4 && cq >= 1 && (cq & (cq - 1)) == 0 && cq <= kThreads) {
-    int cshift = 0;
-    while ((1 << cshift) < cq) ++cshift;
-    hipLaunchKernelGGL(affine_act_fwd_cs_k, dim3(msk_ew_blocks(voxels * cq / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0, ctx->stream,
-                       (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, (float*)out.p,
-                       out.ld, voxels, x.c, cshift, alpha_in, (unsigned*)out_amax, (float*)out2.p, out2.ld);
-    MSK_LAUNCH_CHECK(ctx);
-    return 0;
-  } else if (out2.p) {
+  if (sel.form != EwForm::CS && out2.p) {
     return msk_fail(ctx, __FILE__, __LINE__, "msk_affine_act_fwd_amax2", "the second output needs the channel-stationary float4 kernel (C / 4 a power of two, aligned tensors)");
-  } else if (v4) {
+  } else if (sel.form == EwForm::D12) {
+    const long groups = voxels * x.c / 12;
+    d12_ladder(x.c, [&](auto c) {
+      hipLaunchKernelGGL(affine_act_fwd_d12_k<decltype(c)::value>, dim3(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
+                         ctx->stream, (const float*)x.p, scale, shift, (const float*)res.p, alpha, (float*)out.p, groups,
+                         (unsigned*)out_amax);
+    });
+  } else if (sel.form == EwForm::CS) {
+    hipLaunchKernelGGL(affine_act_fwd_cs_k, dim3(msk_ew_blocks(voxels * (x.c / 4) / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0, ctx->stream,
+                       (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, (float*)out.p,
+                       out.ld, voxels, x.c, sel.cshift, alpha_in, (unsigned*)out_amax, (float*)out2.p, out2.ld);
+  } else if (sel.form == EwForm::K4) {
     hipLaunchKernelGGL(affine_act_fwd_k<4>, dim3(msk_ew_blocks(voxels * x.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, (float*)out.p, out.ld, voxels, x.c, alpha_in, (unsigned*)out_amax);
@@ -1442,69 +1497,35 @@ int msk_affine_act_bwd_reduce_pg(msk_ctx* ctx, msk_tensor x, const float* scale,
                                  float* sums, float* maxes, int clear_maxes, float* dgamma, float* dbeta, float* dalpha) {
   MSK_REQUIRE(ctx, msk_same_shape(x, dout), "x/dout shape mismatch");
   const long voxels = msk_voxels(x);
-  const bool v4 = x.c % 4 == 0 && x.c / 4 <= kThreads && vec4_ok(x) && vec4_ok(dout) &&
-                  (res.p == nullptr || res.c != x.c || vec4_ok(res));
+  const ReducePlan p = reduce_plan(PassTensors{x, res, dout}, voxels, ctx->num_cu, 1);
   if (maxes) {
-    MSK_REQUIRE(ctx, v4, "maxes are produced by the float4 kernel only: channel count and strides multiples of 4, 16-byte aligned tensors");
+    MSK_REQUIRE(ctx, p.form == RedForm::V4, "maxes are produced by the float4 kernel only: channel count and strides multiples of 4, 16-byte aligned tensors");
     if (clear_maxes) MSK_CHECK_HIP(ctx, hipMemsetAsync(maxes, 0, 2 * kWbfAmaxWays * sizeof(float), ctx->stream));
   }
-  if (v4) {
-    const int QCB = pow2ceil(x.c / 4), VL = kThreads / QCB;
-    const int nb = reduce_blocks(voxels, VL, ctx->num_cu, 1);
-    float* partial = (float*)msk_workspace(ctx, (size_t)nb * 3 * 4 * QCB * sizeof(float));
-    if (!partial) return -1;
-    {
-      msk_launch_scope ls(ctx, "affine_act_bwd_reduce");
-      hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<0>, dim3(nb), dim3(kThreads), 0, ctx->stream,
-                         (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean, invstd,
-                         (const float*)dout.p, dout.ld, voxels, x.c, QCB, VL, (float*)nullptr, 0, (float*)nullptr, 0, 0,
-                         partial, (unsigned*)maxes, (const float*)nullptr);
-      MSK_LAUNCH_CHECK(ctx);
-    }
-    msk_launch_scope ls(ctx, "sums_merge");
-    hipLaunchKernelGGL(sums_merge_k, dim3(3 * x.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, x.c, 4 * QCB, 3, sums, 0, dbeta, dgamma,
-                       dalpha, (float*)nullptr);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
-  }
-  ChanGeom g = chan_geom(x.c);
-  int nb = reduce_blocks(voxels, g.VPB, ctx->num_cu, 1);
-  size_t bytes = (size_t)g.cblocks * nb * 3 * g.CB * sizeof(float);
-  float* partial = (float*)msk_workspace(ctx, bytes);
+  float* partial = (float*)msk_workspace(ctx, p.bytes(3));
   if (!partial) return -1;
-  if (g_dense12 && d12_shape(x, voxels) && d12_ok(x) && d12_ok(dout) && (res.p == nullptr || (res.c == x.c && d12_ok(res)))) {
-    const long groups = voxels * x.c / 12;
-    {
-      msk_launch_scope ls(ctx, "affine_act_bwd_reduce");
-#define D12_RD(C_) hipLaunchKernelGGL((affine_act_bwd_reduce_d12_k<C_, 3>), dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p, scale, shift, \
-                                      (const float*)res.p, alpha, mean, invstd, (const float*)dout.p, groups, g.CB, partial)
-      if (x.c == 1) D12_RD(1); else if (x.c == 2) D12_RD(2); else if (x.c == 3) D12_RD(3); else D12_RD(6);
-#undef D12_RD
-      MSK_LAUNCH_CHECK(ctx);
-    }
-    msk_launch_scope ls(ctx, "sums_merge");
-    hipLaunchKernelGGL(sums_merge_k, dim3(3 * x.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, x.c,
-                       g.CB, 3, sums, 0, dbeta, dgamma, dalpha, (float*)nullptr);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
-  }
   {
     msk_launch_scope ls(ctx, "affine_act_bwd_reduce");
-    hipLaunchKernelGGL(affine_act_bwd_reduce_k, dim3(nb, g.cblocks), dim3(kThreads), 0, ctx->stream,
-                       (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean,
-                       invstd, (const float*)dout.p, dout.ld, voxels, x.c, g.CB, g.VPB, partial);
+    if (p.form == RedForm::V4) {
+      hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<0>, dim3(p.nb), dim3(kThreads), 0, ctx->stream,
+                         (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean, invstd,
+                         (const float*)dout.p, dout.ld, voxels, x.c, p.lanes, p.rows, (float*)nullptr, 0, (float*)nullptr, 0, 0,
+                         partial, (unsigned*)maxes, (const float*)nullptr);
+    } else if (p.form == RedForm::D12) {
+      const long groups = voxels * x.c / 12;
+      d12_ladder(x.c, [&](auto c) {
+        hipLaunchKernelGGL((affine_act_bwd_reduce_d12_k<decltype(c)::value, 3>), dim3(p.nb), dim3(kThreads), 0, ctx->stream,
+                           (const float*)x.p, scale, shift, (const float*)res.p, alpha, mean, invstd, (const float*)dout.p, groups,
+                           p.stride, partial);
+      });
+    } else {
+      hipLaunchKernelGGL(affine_act_bwd_reduce_k, dim3(p.nb, p.cblocks), dim3(kThreads), 0, ctx->stream,
+                         (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean,
+                         invstd, (const float*)dout.p, dout.ld, voxels, x.c, p.lanes, p.rows, partial);
+    }
     MSK_LAUNCH_CHECK(ctx);
   }
-  {
-    msk_launch_scope ls(ctx, "sums_merge");
-    hipLaunchKernelGGL(sums_merge_k, dim3(3 * x.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, x.c,
-                       g.CB, 3, sums, 0, dbeta, dgamma, dalpha, (float*)nullptr);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-  }
-  return 0;
+  return sums_merge_tail(ctx, partial, p.nb, x.c, p.stride, 3, sums, 0, dbeta, dgamma, dalpha);
 }
 
 int msk_affine_act_bwd_apply(msk_ctx* ctx, msk_tensor x, const float* scale, const float* shift, msk_tensor res,
@@ -1526,31 +1547,22 @@ int msk_affine_act_bwd_apply_amax(msk_ctx* ctx, msk_tensor x, const float* scale
   if (bn_mode == 1) MSK_REQUIRE(ctx, sums_total && mean && invstd && scale, "training BN backward needs sums/mean/invstd/scale");
   if (bn_mode == 2) MSK_REQUIRE(ctx, scale != nullptr, "eval BN backward needs scale");
   const long voxels = msk_voxels(x);
-  const bool v4 = vec4_ok(x) && vec4_ok(dout) && vec4_ok(dx) && vec4_ok(dres) &&
-                  (res.p == nullptr || res.c != x.c || vec4_ok(res));
+  const EwSel sel = ew_select(PassTensors{x, res, dout, dx, dres}, voxels, false);
   const float invM = (float)(1.0 / M_total);
   msk_launch_scope ls(ctx, "affine_act_bwd_apply");
-  const int cq = x.c / 4;
-  if (g_dense12 && !v4 && d12_shape(x, voxels) && d12_ok(x) && d12_ok(dout) && d12_ok(dx) && d12_ok(dres) &&
-      (res.p == nullptr || (res.c == x.c && d12_ok(res)))) {
+  if (sel.form == EwForm::D12) {
     const long groups = voxels * x.c / 12;
-    const dim3 grid(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap));
-#define D12_AP(C_) hipLaunchKernelGGL(affine_act_bwd_apply_d12_k<C_>, grid, dim3(kThreads), 0, ctx->stream, (const float*)x.p, scale, shift, \
-                                      (const float*)res.p, alpha, mean, invstd, (const float*)dout.p, sums_total, invM, bn_mode, (float*)dx.p, \
-                                      (float*)dres.p, dres_acc, groups, x.c, (unsigned*)dx_amax)
-    if (x.c == 1) D12_AP(1); else if (x.c == 2) D12_AP(2); else if (x.c == 3) D12_AP(3); else D12_AP(6);
-#undef D12_AP
-    MSK_LAUNCH_CHECK(ctx);
-    return 0;
-  }
-  if (v4 && cq >= 1 && (cq & (cq - 1)) == 0 && cq <= kThreads) {
-    int cshift = 0;
-    while ((1 << cshift) < cq) ++cshift;
-    hipLaunchKernelGGL(affine_act_bwd_apply_cs_k, dim3(msk_ew_blocks(voxels * cq / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
+    d12_ladder(x.c, [&](auto c) {
+      hipLaunchKernelGGL(affine_act_bwd_apply_d12_k<decltype(c)::value>, dim3(msk_ew_blocks(groups, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
+                         ctx->stream, (const float*)x.p, scale, shift, (const float*)res.p, alpha, mean, invstd, (const float*)dout.p,
+                         sums_total, invM, bn_mode, (float*)dx.p, (float*)dres.p, dres_acc, groups, x.c, (unsigned*)dx_amax);
+    });
+  } else if (sel.form == EwForm::CS) {
+    hipLaunchKernelGGL(affine_act_bwd_apply_cs_k, dim3(msk_ew_blocks(voxels * (x.c / 4) / 2, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c, alpha, mean,
                        invstd, (const float*)dout.p, dout.ld, sums_total, invM, bn_mode, (float*)dx.p, dx.ld,
-                       (float*)dres.p, dres.ld, dres_acc, voxels, x.c, cshift, (unsigned*)dx_amax);
-  } else if (v4) {
+                       (float*)dres.p, dres.ld, dres_acc, voxels, x.c, sel.cshift, (unsigned*)dx_amax);
+  } else if (sel.form == EwForm::K4) {
     hipLaunchKernelGGL(affine_act_bwd_apply_k<4>, dim3(msk_ew_blocks(voxels * x.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads),
                        0, ctx->stream, (const float*)x.p, x.ld, scale, shift, (const float*)res.p, res.ld, res.c,
                        alpha, mean, invstd, (const float*)dout.p, dout.ld, sums_total, invM, bn_mode,
@@ -1575,46 +1587,34 @@ static int add_act_bwd_impl(msk_ctx* ctx, msk_tensor a, const float* scale, cons
   MSK_REQUIRE(ctx, msk_same_shape(a, b) && msk_same_shape(a, dout) && msk_same_shape(a, da) && (!db.p || msk_same_shape(a, db)), "shape mismatch");
   MSK_REQUIRE(ctx, db.p || !db_accumulate, "a skipped second gradient cannot accumulate");
   MSK_REQUIRE(ctx, alpha != nullptr && dalpha != nullptr, "join needs alpha and its gradient");
-  MSK_REQUIRE(ctx, a.c % 4 == 0 && a.c / 4 <= kThreads && vec4_ok(a) && vec4_ok(b) && vec4_ok(dout) && vec4_ok(da) &&
-                       (!db.p || vec4_ok(db)), "join backward needs float4-aligned tensors with C % 4 == 0");
   const long voxels = msk_voxels(a);
-  const int QCB = pow2ceil(a.c / 4), VL = kThreads / QCB;
-  const int nb = reduce_blocks(voxels, VL, ctx->num_cu, 2);
-  if (unit_sums) {  // the unit's BatchNorm/PReLU sums in the same pass
-    float* partial4 = (float*)msk_workspace(ctx, (size_t)nb * 4 * 4 * QCB * sizeof(float));
-    if (!partial4) return -1;
+  const ReducePlan p = reduce_plan(PassTensors{a, b, dout, da, db}, voxels, ctx->num_cu, 2);
+  MSK_REQUIRE(ctx, p.form == RedForm::V4, "join backward needs float4-aligned tensors with C % 4 == 0");
+  const int nq = unit_sums ? 4 : 1;   // the unit's BatchNorm/PReLU sums in the same pass
+  float* partial = (float*)msk_workspace(ctx, p.bytes(nq));
+  if (!partial) return -1;
+  if (unit_sums) {
     if (maxes && clear_maxes) MSK_CHECK_HIP(ctx, hipMemsetAsync(maxes, 0, 2 * kWbfAmaxWays * sizeof(float), ctx->stream));
     {
       msk_launch_scope ls(ctx, "add_act_bwd_unit");
-      hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<2>, dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)a.p, a.ld, scale,
-                         shift, (const float*)b.p, b.ld, b.c, alpha, mean, invstd, (const float*)dout.p, dout.ld, voxels, a.c, QCB,
-                         VL, (float*)da.p, da.ld, (float*)db.p, db.ld, db_accumulate, partial4, (unsigned*)maxes, alpha_in);
+      hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<2>, dim3(p.nb), dim3(kThreads), 0, ctx->stream, (const float*)a.p, a.ld, scale,
+                         shift, (const float*)b.p, b.ld, b.c, alpha, mean, invstd, (const float*)dout.p, dout.ld, voxels, a.c, p.lanes,
+                         p.rows, (float*)da.p, da.ld, (float*)db.p, db.ld, db_accumulate, partial, (unsigned*)maxes, alpha_in);
       MSK_LAUNCH_CHECK(ctx);
     }
-    msk_launch_scope ls(ctx, "sums_merge");
     // quantities 0..2 -> unit_sums[3C] (overwritten), quantity 3 -> dalpha of the join (accumulated)
     // ... and the parameter gradients ride along: the unit's (d beta, d gamma, d alpha_inner; nullable) and the join's d alpha
-    hipLaunchKernelGGL(sums_merge_k, dim3(4 * a.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial4, nb, a.c, 4 * QCB, 4, unit_sums, 0, u_dbeta,
-                       u_dgamma, u_dalpha, dalpha);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
+    return sums_merge_tail(ctx, partial, p.nb, a.c, p.stride, 4, unit_sums, 0, u_dbeta, u_dgamma, u_dalpha, dalpha);
   }
-  float* partial = (float*)msk_workspace(ctx, (size_t)nb * 4 * QCB * sizeof(float));
-  if (!partial) return -1;
   {
     msk_launch_scope ls(ctx, "add_act_bwd");
-    hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<1>, dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)a.p,
+    hipLaunchKernelGGL(affine_act_bwd_reduce_v4_k<1>, dim3(p.nb), dim3(kThreads), 0, ctx->stream, (const float*)a.p,
                        a.ld, scale, shift, (const float*)b.p, b.ld, b.c, alpha,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)dout.p, dout.ld, voxels, a.c, QCB, VL,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)dout.p, dout.ld, voxels, a.c, p.lanes, p.rows,
                        (float*)da.p, da.ld, (float*)db.p, db.ld, db_accumulate, partial, (unsigned*)nullptr, alpha_in);
     MSK_LAUNCH_CHECK(ctx);
   }
-  msk_launch_scope ls(ctx, "sums_merge");
-  hipLaunchKernelGGL(sums_merge_k, dim3(a.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, a.c, 4 * QCB, 1, dalpha, 1);
-  MSK_LAUNCH_CHECK(ctx);
-  noop_launches(ctx);
-  return 0;
+  return sums_merge_tail(ctx, partial, p.nb, a.c, p.stride, 1, dalpha, 1);
 }
 
 int msk_add_act_bwd(msk_ctx* ctx, msk_tensor a, msk_tensor b, const float* alpha, msk_tensor dout, msk_tensor da,
@@ -1674,7 +1674,7 @@ int msk_copy_scale_amax(msk_ctx* ctx, msk_tensor src, const float* mask, msk_ten
   const long voxels = msk_voxels(src);
   const long vpn = (long)src.d * src.h * src.w;
   msk_launch_scope ls(ctx, "copy_scale");
-  if (vec4_ok(src) && vec4_ok(dst)) {
+  if (pass_v4(PassTensors{src, msk_tensor{}, dst})) {   // K4 | K1: no channel-stationary or dense-12 form of the copy
     hipLaunchKernelGGL(copy_scale_k<4>, dim3(msk_ew_blocks(voxels * src.c / 4, ctx->num_cu, g_ew_cap)), dim3(kThreads), 0,
                        ctx->stream, (const float*)src.p, src.ld, mask, (float*)dst.p, dst.ld, voxels, vpn, src.c,
                        accumulate, (unsigned*)dst_amax);
@@ -1698,42 +1698,25 @@ int msk_dropout_mask(msk_ctx* ctx, uint64_t seed, uint64_t step, uint32_t site, 
 
 int msk_channel_sum(msk_ctx* ctx, msk_tensor x, float* out, int accumulate) {
   const long voxels = msk_voxels(x);
-  ChanGeom g = chan_geom(x.c);
-  int nb = reduce_blocks(voxels, g.VPB, ctx->num_cu, 3);
-  float* partial = (float*)msk_workspace(ctx, (size_t)g.cblocks * nb * g.CB * sizeof(float));
+  const ReducePlan p = reduce_plan(PassTensors{x}, voxels, ctx->num_cu, 3, /*has_v4=*/false);
+  float* partial = (float*)msk_workspace(ctx, p.bytes(1));
   if (!partial) return -1;
-  if (g_dense12 && d12_shape(x, voxels) && d12_ok(x)) {
-    const long groups = voxels * x.c / 12;
-    {
-      msk_launch_scope ls(ctx, "channel_sum_partial");
-#define D12_CS(C_) hipLaunchKernelGGL((affine_act_bwd_reduce_d12_k<C_, 1>), dim3(nb), dim3(kThreads), 0, ctx->stream, (const float*)x.p, (const float*)nullptr, \
-                                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, \
-                                      (const float*)nullptr, groups, g.CB, partial)
-      if (x.c == 1) D12_CS(1); else if (x.c == 2) D12_CS(2); else if (x.c == 3) D12_CS(3); else D12_CS(6);
-#undef D12_CS
-      MSK_LAUNCH_CHECK(ctx);
-    }
-    msk_launch_scope ls(ctx, "sums_merge");
-    hipLaunchKernelGGL(sums_merge_k, dim3(x.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, x.c, g.CB, 1,
-                       out, accumulate);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-    return 0;
-  }
   {
     msk_launch_scope ls(ctx, "channel_sum_partial");
-    hipLaunchKernelGGL(channel_sum_partial_k, dim3(nb, g.cblocks), dim3(kThreads), 0, ctx->stream,
-                       (const float*)x.p, x.ld, voxels, x.c, g.CB, g.VPB, partial);
+    if (p.form == RedForm::D12) {   // the backward reduction's kernel with one quantity: the plain sum
+      const long groups = voxels * x.c / 12;
+      const float* const none = nullptr;
+      d12_ladder(x.c, [&](auto c) {
+        hipLaunchKernelGGL((affine_act_bwd_reduce_d12_k<decltype(c)::value, 1>), dim3(p.nb), dim3(kThreads), 0, ctx->stream,
+                           (const float*)x.p, none, none, none, none, none, none, none, groups, p.stride, partial);
+      });
+    } else {
+      hipLaunchKernelGGL(channel_sum_partial_k, dim3(p.nb, p.cblocks), dim3(kThreads), 0, ctx->stream,
+                         (const float*)x.p, x.ld, voxels, x.c, p.lanes, p.rows, partial);
+    }
     MSK_LAUNCH_CHECK(ctx);
   }
-  {
-    msk_launch_scope ls(ctx, "sums_merge");
-    hipLaunchKernelGGL(sums_merge_k, dim3(x.c), dim3(nb > 256 ? 256 : 64), 0, ctx->stream, partial, nb, x.c, g.CB, 1,
-                       out, accumulate);
-    MSK_LAUNCH_CHECK(ctx);
-    noop_launches(ctx);
-  }
-  return 0;
+  return sums_merge_tail(ctx, partial, p.nb, x.c, p.stride, 1, out, accumulate);
 }
 
 int msk_softmax_c(msk_ctx* ctx, msk_tensor x, msk_tensor out) {
@@ -1937,12 +1920,10 @@ extern "C" {
 int msk_elu_fwd(msk_ctx* ctx, msk_tensor x, float alpha, msk_tensor out) {
   MSK_REQUIRE(ctx, x.c == out.c && msk_voxels(x) == msk_voxels(out), "shape mismatch");
   const long voxels = msk_voxels(x);
-  long blocks = (voxels * x.c + kThreads - 1) / kThreads;
-  if (blocks > 16L * ctx->num_cu) blocks = 16L * ctx->num_cu;
-  if (blocks < 1) blocks = 1;
   msk_launch_scope ls(ctx, "elu_fwd");
-  hipLaunchKernelGGL(elu_fwd_k, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, (const float*)x.p, x.ld, (float*)out.p, out.ld,
-                     x.c, voxels, alpha);
+  // msk_ew_blocks' own 16 blocks per CU, not option "ew_cap"
+  hipLaunchKernelGGL(elu_fwd_k, dim3(msk_ew_blocks(voxels * x.c, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, (const float*)x.p, x.ld,
+                     (float*)out.p, out.ld, x.c, voxels, alpha);
   MSK_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1950,11 +1931,8 @@ int msk_elu_bwd(msk_ctx* ctx, msk_tensor out, msk_tensor dout, float alpha, msk_
   MSK_REQUIRE(ctx, out.c == dout.c && out.c == dx.c && msk_voxels(out) == msk_voxels(dout) && msk_voxels(out) == msk_voxels(dx),
               "shape mismatch");
   const long voxels = msk_voxels(out);
-  long blocks = (voxels * out.c + kThreads - 1) / kThreads;
-  if (blocks > 16L * ctx->num_cu) blocks = 16L * ctx->num_cu;
-  if (blocks < 1) blocks = 1;
   msk_launch_scope ls(ctx, "elu_bwd");
-  hipLaunchKernelGGL(elu_bwd_k, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, (const float*)out.p, out.ld,
+  hipLaunchKernelGGL(elu_bwd_k, dim3(msk_ew_blocks(voxels * out.c, ctx->num_cu)), dim3(kThreads), 0, ctx->stream, (const float*)out.p, out.ld,
                      (const float*)dout.p, dout.ld, (float*)dx.p, dx.ld, out.c, voxels, alpha, accumulate);
   MSK_LAUNCH_CHECK(ctx);
   return 0;

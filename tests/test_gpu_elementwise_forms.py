@@ -157,7 +157,8 @@ def _d12_shape(x):
 
 def _elementwise_form(x, others, res, d12_allowed=True):
     """msk_affine_act_fwd / _join_fwd (d12_allowed False: alpha_in or out2) and msk_affine_act_bwd_apply: x, the other
-    full-size tensors (out | dout, dx, dres), the residual"""
+    full-size tensors (out | dout, dx, dres), the residual.  The mirror of ew_select in msk_elementwise.hip; the comment block
+    "Which form of a pass runs" above it states the order of the forms and why it agrees with _reduce_form's."""
     v4 = all(_vec4_ok(t) for t in [x] + others) and (res is None or res.c != x.c or _vec4_ok(res))
     if (dev().get_option("dense12") and not v4 and d12_allowed and _d12_shape(x) and all(_d12_ok(t) for t in [x] + others)
             and (res is None or (res.c == x.c and _d12_ok(res)))):
@@ -169,7 +170,8 @@ def _elementwise_form(x, others, res, d12_allowed=True):
 
 
 def _reduce_form(x, dout, res):
-    """msk_affine_act_bwd_reduce_ex; with dout None: msk_bn_stats"""
+    """msk_affine_act_bwd_reduce_ex; with dout None: msk_bn_stats.  The mirror of reduce_plan's form in msk_elementwise.hip
+    (same comment block: "Which form of a pass runs")."""
     o = [t for t in (x, dout) if t is not None]
     if x.c % 4 == 0 and x.c // 4 <= 256 and all(_vec4_ok(t) for t in o) and (res is None or res.c != x.c or _vec4_ok(res)):
         return "v4"
@@ -179,6 +181,7 @@ def _reduce_form(x, dout, res):
 
 
 def _copy_form(src, dst):
+    """msk_copy_scale: pass_v4 of the same block, the K4 / K1 half of ew_select"""
     return "k4" if _vec4_ok(src) and _vec4_ok(dst) else "k1"
 
 
