@@ -543,6 +543,35 @@ int msk_patch_crop(msk_ctx* ctx, const void* src, int d, int h, int w, const int
 int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
                      const float* matrix, float* out_img, int32_t* out_label, int rd, int rh, int rw, float pad,
                      int32_t label_pad);
+/* Elastic deformation of that sampling grid (replaces batchgenerators' elastic_deform_coordinates, the third part of its
+ * SpatialTransform, and MONAI's Rand3DElastic; not in the reference), as tests/elastic_reference.py states it.
+ *
+ * msk_elastic_field: field (DEVICE, float32 [3][rd][rh][rw]) = alpha * (uniform noise smoothed by a Gaussian).  With
+ * n = rd*rh*rw and key = splitmix64(seed), component a at patch voxel v = (z*rh + y)*rw + x starts as
+ *     u = (float)(splitmix64(key + a*n + v) >> 40) * 2^-23 - 1        (exact, in [-1, 1))
+ * and is filtered along w, then h, then d with the HOST taps (2r+1 floats, preprocess.gauss_taps) and zeros outside the patch
+ * (scipy's mode='constant'): acc = taps[0]*x[i-r], then acc = acc + taps[k]*x[i-r+k] for k = 1..2r -- all 2r+1 terms, an operand
+ * outside the line is +0.0 -- and finally multiplied by alpha; every multiply and add is a float32 operation rounded on its own.
+ * A component whose bit is clear in axes_mask (bit a = source axis a) is +0.0 everywhere; the others do not depend on the mask.
+ * scratch (DEVICE) has the size of field.  The noise is generated inside the first pass, no noise buffer exists.  Up to three
+ * launches and two clears on the context stream; no atomics, no synchronisation, no download; two calls give the same bits.
+ * Argument errors, reported before any launch: null pointers; r outside [2, 64]; alpha not finite or outside [0, 4096];
+ * axes_mask outside [0, 7]; extents < 1 or > 8192; 3*n >= 2^31; misaligned pointers (4 bytes); field overlapping scratch; a
+ * tap that is not finite or outside [0, 1].
+ *
+ * msk_affine_patch_elastic: msk_affine_patch whose offsets are displaced before the matrix (batchgenerators' order: the
+ * zero-centred mesh is deformed, then rotated and scaled, then moved to the centre):
+ *     e_a = o_a + field[a][z][y][x]                                    (one float32 add per axis)
+ *     p_a = ((M[a][0]*e_z + M[a][1]*e_y) + M[a][2]*e_x) + (float)(origin_a + roi_a/2)
+ * and everything from p on as msk_affine_patch; a field of +0.0 gives msk_affine_patch's bits.  With msk_elastic_field's
+ * |field| <= 4096 this bounds |p| below 2^18; whatever the field holds, every index is clamped into the volume before it is
+ * used.  Argument errors: those of msk_affine_patch, and a null or misaligned field, 3*rd*rh*rw >= 2^31, an output overlapping
+ * field.                                                                                                                   */
+int msk_elastic_field(msk_ctx* ctx, uint64_t seed, int rd, int rh, int rw, const float* taps, int r, float alpha, int axes_mask,
+                      float* field, float* scratch);
+int msk_affine_patch_elastic(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
+                             const float* matrix, const float* field, float* out_img, int32_t* out_label, int rd, int rh, int rw,
+                             float pad, int32_t label_pad);
 
 /* ---- intensity augmentation (transforms.RandomGaussianNoise3D / RandomGaussianBlur3D / RandomBrightness3D /
  *      RandomContrast3D / RandomGamma3D; no reference call site: the reference has geometric augmentation only) ---- */

@@ -140,6 +140,8 @@ SIGNATURES = {
     "msk_patch_select": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "msk_patch_crop": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _u32]),
     "msk_affine_patch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_int32]),
+    "msk_elastic_field": (_i, [_vp, _u64, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
+    "msk_affine_patch_elastic": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_int32]),
     "msk_intensity_stats_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
     "msk_intensity_stats": (_i, [_vp, _vp, C.c_long, _vp, _vp]),
     "msk_intensity_apply": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp, _vp, _u64]),

@@ -13,6 +13,10 @@
 // coordinate chain is v_mul_f32 / v_add_f32 and the seven lerps are v_sub_f32 / v_mul_f32 / v_add_f32; the kernels hold no
 // v_fma_f32, v_fmac_f32 or v_mad_f32 at all.
 //
+// msk_affine_patch_elastic is the same voxel routine with one more template parameter: the three offsets are displaced by the
+// field of msk_elastic_field (msk_elastic.hip) before the matrix, e_a = o_a + F_a, one add per axis (tests/elastic_reference.py).
+// The instantiations without it are the code they were.
+//
 // One launch, one thread per output voxel, no atomics, no LDS.  A corner outside the volume is never loaded from there: its
 // index is clamped into the volume (so all eight loads are unconditional and in flight together) and the value is replaced by
 // the pad with a select.  Two thread -> voxel maps (context option "affine_map", A/B; DESIGN.md section 7 has both times):
@@ -44,13 +48,26 @@ __device__ __forceinline__ float lerp(float a, float b, float t) { return a + t 
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-template <bool kLabel>
+// kElastic: the offset is displaced by the field [3][rd][rh][rw] of msk_elastic_field before the matrix (batchgenerators'
+// order: deform the zero-centred mesh, then rotate and scale it, then move it to the centre)
+template <bool kLabel, bool kElastic>
 __device__ __forceinline__ void affine_voxel(const float* __restrict__ img, const int32_t* __restrict__ label,
-                                             const int32_t* __restrict__ sel, float* __restrict__ out_img,
-                                             int32_t* __restrict__ out_label, const AffineArgs& g, int z, int y, int x) {
+                                             const int32_t* __restrict__ sel, const float* __restrict__ field,
+                                             float* __restrict__ out_img, int32_t* __restrict__ out_label, const AffineArgs& g,
+                                             int z, int y, int x) {
   const float cd = (float)(sel[0] + g.rd / 2), ch = (float)(sel[1] + g.rh / 2), cw = (float)(sel[2] + g.rw / 2);
-  const float oz = (float)(z - g.rd / 2), oy = (float)(y - g.rh / 2), ox = (float)(x - g.rw / 2);
-  // |p| <= 3 * 4 * 8192 + 2 * 8192 < 2^17: the conversions below are defined
+  float oz = (float)(z - g.rd / 2), oy = (float)(y - g.rh / 2), ox = (float)(x - g.rw / 2);
+  const long o = ((long)z * g.rh + y) * g.rw + x;
+  if (kElastic) {
+    const long n = (long)g.rd * g.rh * g.rw;
+    oz = oz + field[o];
+    oy = oy + field[n + o];
+    ox = ox + field[2 * n + o];
+  }
+  // without a field |o| <= 8192 and |p| <= 3 * 4 * 8192 + 2 * 8192 < 2^17; with msk_elastic_field's |F| <= 4096 (alpha <= 4096,
+  // |smoothed u| <= 1 up to rounding) |e| <= 8192 + 4096 and |p| <= 3 * 4 * 12288 + 2 * 8192 < 2^18: the conversions below are
+  // defined.  For any other field content (NaN and infinities included) v_cvt_i32_f32 saturates and every index is clamped
+  // into the volume before it is used, so no address leaves the volume.
   const float pd = ((g.m[0] * oz + g.m[1] * oy) + g.m[2] * ox) + cd;
   const float ph = ((g.m[3] * oz + g.m[4] * oy) + g.m[5] * ox) + ch;
   const float pw = ((g.m[6] * oz + g.m[7] * oy) + g.m[8] * ox) + cw;
@@ -85,46 +102,55 @@ __device__ __forceinline__ void affine_voxel(const float* __restrict__ img, cons
   const float v110 = vd1 && vh1 && vw0 ? l110 : pad, v111 = vd1 && vh1 && vw1 ? l111 : pad;
   const float c00 = lerp(v000, v001, tw), c01 = lerp(v010, v011, tw);
   const float c10 = lerp(v100, v101, tw), c11 = lerp(v110, v111, tw);
-  const long o = ((long)z * g.rh + y) * g.rw + x;
   out_img[o] = lerp(lerp(c00, c01, th), lerp(c10, c11, th), td);
   if (kLabel) out_label[o] = lab_in ? lab : g.label_pad;
 }
 
 // row-linear: threads cover the flattened patch
-template <bool kLabel>
+template <bool kLabel, bool kElastic>
 __global__ void __launch_bounds__(kThreads)
 affine_rows_k(const float* __restrict__ img, const int32_t* __restrict__ label, const int32_t* __restrict__ sel,
-              float* __restrict__ out_img, int32_t* __restrict__ out_label, AffineArgs g) {
+              const float* __restrict__ field, float* __restrict__ out_img, int32_t* __restrict__ out_label, AffineArgs g) {
   const unsigned total = (unsigned)g.rd * (unsigned)g.rh * (unsigned)g.rw;
   const unsigned i = blockIdx.x * (unsigned)kThreads + threadIdx.x;
   if (i >= total) return;
   const unsigned r = i / (unsigned)g.rw, x = i - r * (unsigned)g.rw;
   const unsigned z = r / (unsigned)g.rh, y = r - z * (unsigned)g.rh;
-  affine_voxel<kLabel>(img, label, sel, out_img, out_label, g, (int)z, (int)y, (int)x);
+  affine_voxel<kLabel, kElastic>(img, label, sel, field, out_img, out_label, g, (int)z, (int)y, (int)x);
 }
 
 // tile: blockIdx.x = x box, blockIdx.y = y box, blockIdx.z = z box; lane bits 0-3 x, 4 y, 5 z, wavefront bits y, z
-template <bool kLabel>
+template <bool kLabel, bool kElastic>
 __global__ void __launch_bounds__(kThreads)
 affine_tile_k(const float* __restrict__ img, const int32_t* __restrict__ label, const int32_t* __restrict__ sel,
-              float* __restrict__ out_img, int32_t* __restrict__ out_label, AffineArgs g) {
+              const float* __restrict__ field, float* __restrict__ out_img, int32_t* __restrict__ out_label, AffineArgs g) {
   const int t = threadIdx.x;
   const int x = (int)blockIdx.x * kTileX + (t & 15);
   const int y = (int)blockIdx.y * kTileY + ((t >> 4) & 1) + ((t >> 6) & 1) * 2;
   const int z = (int)blockIdx.z * kTileZ + ((t >> 5) & 1) + ((t >> 7) & 1) * 2;
   if (x >= g.rw || y >= g.rh || z >= g.rd) return;
-  affine_voxel<kLabel>(img, label, sel, out_img, out_label, g, z, y, x);
+  affine_voxel<kLabel, kElastic>(img, label, sel, field, out_img, out_label, g, z, y, x);
 }
 
 inline bool extents_ok(int d, int h, int w) {
   return d >= 1 && h >= 1 && w >= 1 && d <= kMaxExtent && h <= kMaxExtent && w <= kMaxExtent;
 }
-}  // namespace
+template <bool kLabel, bool kElastic>
+void launch_affine(msk_ctx* ctx, const float* img, const int32_t* label, const int32_t* sel, const float* field, float* out_img,
+                   int32_t* out_label, const AffineArgs& g) {
+  // grid.y and grid.z hold at most 8192 / 4 boxes
+  const dim3 boxes((unsigned)msk_cdiv(g.rw, kTileX), (unsigned)msk_cdiv(g.rh, kTileY), (unsigned)msk_cdiv(g.rd, kTileZ));
+  const dim3 rows((unsigned)msk_cdiv((long)g.rd * g.rh * g.rw, kThreads));
+  if (ctx->affine_map != 0)
+    hipLaunchKernelGGL((affine_tile_k<kLabel, kElastic>), boxes, dim3(kThreads), 0, ctx->stream, img, label, sel, field, out_img, out_label, g);
+  else
+    hipLaunchKernelGGL((affine_rows_k<kLabel, kElastic>), rows, dim3(kThreads), 0, ctx->stream, img, label, sel, field, out_img, out_label, g);
+}
 
-extern "C" {
-
-int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
-                     const float* matrix, float* out_img, int32_t* out_label, int rd, int rh, int rw, float pad, int32_t label_pad) {
+// msk_affine_patch (field == nullptr, elastic false) and msk_affine_patch_elastic: one set of checks, one voxel routine
+int affine_patch(msk_ctx* ctx, const char* tag, bool elastic, const float* img, const int32_t* label, int d, int h, int w,
+                 const int32_t* sel, const float* matrix, const float* field, float* out_img, int32_t* out_label, int rd, int rh,
+                 int rw, float pad, int32_t label_pad) {
   MSK_REQUIRE(ctx, ctx != nullptr, "null context");
   MSK_REQUIRE(ctx, img != nullptr && sel != nullptr && matrix != nullptr && out_img != nullptr, "null img / sel / matrix / out_img");
   MSK_REQUIRE(ctx, (label != nullptr) == (out_label != nullptr), "label and out_label must both be set or both be null");
@@ -146,27 +172,41 @@ int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d
                          msk_bytes_disjoint(out_label, pbytes, sel, 12), "out_label must not overlap img, label or sel");
     MSK_REQUIRE(ctx, msk_bytes_disjoint(out_label, pbytes, out_img, pbytes), "out_label must not overlap out_img");
   }
+  if (elastic) {
+    MSK_REQUIRE(ctx, field != nullptr && (((uintptr_t)field) & 3) == 0, "field must be set and 4-byte aligned");
+    MSK_REQUIRE(ctx, 3 * ((long)rd * rh * rw) <= 0x7fffffffL, "the field must have fewer than 2^31 elements");
+    MSK_REQUIRE(ctx, msk_bytes_disjoint(out_img, pbytes, field, 3 * pbytes), "out_img must not overlap field");
+    if (label != nullptr) MSK_REQUIRE(ctx, msk_bytes_disjoint(out_label, pbytes, field, 3 * pbytes), "out_label must not overlap field");
+  }
   g.D = d; g.H = h; g.W = w;
   g.rd = rd; g.rh = rh; g.rw = rw;
   g.pad = pad;
   g.label_pad = label_pad;
-  msk_launch_scope ls(ctx, "affine_patch");
-  // grid.y and grid.z hold at most 8192 / 4 boxes
-  const dim3 boxes((unsigned)msk_cdiv(rw, kTileX), (unsigned)msk_cdiv(rh, kTileY), (unsigned)msk_cdiv(rd, kTileZ));
-  const dim3 rows((unsigned)msk_cdiv((long)rd * rh * rw, kThreads));
-  if (ctx->affine_map != 0) {
-    if (label != nullptr)
-      hipLaunchKernelGGL(affine_tile_k<true>, boxes, dim3(kThreads), 0, ctx->stream, img, label, sel, out_img, out_label, g);
-    else
-      hipLaunchKernelGGL(affine_tile_k<false>, boxes, dim3(kThreads), 0, ctx->stream, img, label, sel, out_img, out_label, g);
+  msk_launch_scope ls(ctx, tag);
+  if (elastic) {
+    if (label != nullptr) launch_affine<true, true>(ctx, img, label, sel, field, out_img, out_label, g);
+    else launch_affine<false, true>(ctx, img, label, sel, field, out_img, out_label, g);
   } else {
-    if (label != nullptr)
-      hipLaunchKernelGGL(affine_rows_k<true>, rows, dim3(kThreads), 0, ctx->stream, img, label, sel, out_img, out_label, g);
-    else
-      hipLaunchKernelGGL(affine_rows_k<false>, rows, dim3(kThreads), 0, ctx->stream, img, label, sel, out_img, out_label, g);
+    if (label != nullptr) launch_affine<true, false>(ctx, img, label, sel, field, out_img, out_label, g);
+    else launch_affine<false, false>(ctx, img, label, sel, field, out_img, out_label, g);
   }
   MSK_LAUNCH_CHECK(ctx);
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int msk_affine_patch(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
+                     const float* matrix, float* out_img, int32_t* out_label, int rd, int rh, int rw, float pad, int32_t label_pad) {
+  return affine_patch(ctx, "affine_patch", false, img, label, d, h, w, sel, matrix, nullptr, out_img, out_label, rd, rh, rw, pad, label_pad);
+}
+
+int msk_affine_patch_elastic(msk_ctx* ctx, const float* img, const int32_t* label, int d, int h, int w, const int32_t* sel,
+                             const float* matrix, const float* field, float* out_img, int32_t* out_label, int rd, int rh, int rw,
+                             float pad, int32_t label_pad) {
+  return affine_patch(ctx, "affine_patch_elastic", true, img, label, d, h, w, sel, matrix, field, out_img, out_label, rd, rh, rw, pad,
+                      label_pad);
 }
 
 }  // extern "C"

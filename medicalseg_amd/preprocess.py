@@ -396,21 +396,28 @@ def patch_crop_device(vol: DeviceVolume, sel: DeviceVolume, roi, pad=0, index=0)
     return out
 
 
-def affine_patch_device(img: DeviceVolume, label, sel: DeviceVolume, roi, matrix, pad=0, label_pad=0, index=0):
+def affine_patch_device(img: DeviceVolume, label, sel: DeviceVolume, roi, matrix, pad=0, label_pad=0, index=0, field=None):
     """msk_affine_patch: the patch of ``img`` (float32) and, unless ``label`` is None, of ``label`` (int32) whose sampling grid
     is centred on the patch of record ``index`` of ``sel`` (patch_select_device; read on the device) and turned and scaled by
     the 3x3 ``matrix`` (rows: source axes, columns: patch axes) -> one pooled ``DeviceVolume`` of extent ``roi``, or two.  The
     image is read trilinearly with ``pad`` outside the volume, the label by nearest neighbour with ``label_pad``, from the
-    same coordinates, in one launch.  Nothing is downloaded and nothing synchronises."""
+    same coordinates, in one launch.  Nothing is downloaded and nothing synchronises.
+
+    ``field``: a float32 ``DeviceVolume`` of shape ``(3,) + roi`` (elastic_field_device) that displaces the grid before the
+    matrix, msk_affine_patch_elastic; without it the call is msk_affine_patch."""
     _float_volume(img, "affine_patch_device")
+    if field is not None and (not isinstance(field, DeviceVolume) or field.dtype != np.float32 or
+                              tuple(field.shape) != (3,) + tuple(int(r) for r in roi)):
+        raise TypeError("affine_patch_device takes a float32 DeviceVolume of shape (3,) + roi as the field")
     if label is not None and (not isinstance(label, DeviceVolume) or label.dtype != np.int32 or label.shape != img.shape):
         raise TypeError("affine_patch_device takes an int32 DeviceVolume of the image's shape as the label")
     if not 0 <= int(index) < sel.shape[0]:
         raise ValueError("affine_patch_device: record {} of {}".format(index, sel.shape[0]))
     m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float32).reshape(9))
+    name, extra = ("msk_affine_patch", ()) if field is None else ("msk_affine_patch_elastic", (C.c_void_p(field.ptr),))
     with _pooled_outputs(img.dev, (roi, np.float32), None if label is None else (roi, np.int32)) as (out, out_label):
-        img.dev.call("msk_affine_patch", C.c_void_p(img.ptr), C.c_void_p(label.ptr) if label is not None else None, *img.shape,
-                     C.c_void_p(sel.ptr + 32 * int(index)), m.ctypes.data_as(C.c_void_p), C.c_void_p(out.ptr),
+        img.dev.call(name, C.c_void_p(img.ptr), C.c_void_p(label.ptr) if label is not None else None, *img.shape,
+                     C.c_void_p(sel.ptr + 32 * int(index)), m.ctypes.data_as(C.c_void_p), *extra, C.c_void_p(out.ptr),
                      C.c_void_p(out_label.ptr) if label is not None else None, int(roi[0]), int(roi[1]), int(roi[2]),
                      C.c_float(float(pad)), int(label_pad))
     return out if label is None else (out, out_label)
@@ -418,21 +425,52 @@ def affine_patch_device(img: DeviceVolume, label, sel: DeviceVolume, roi, matrix
 
 INTENSITY_NOISE, INTENSITY_SCALE, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_RESTORE = range(5)   # MSK_INTENSITY_*
 GAUSS_MAX_SIGMA = 2.0   # radius int(4 sigma + 0.5) <= 8, the widest msk_gauss_blur3d takes
+ELASTIC_MIN_SIGMA, ELASTIC_MAX_SIGMA = 0.5, 16.0   # radius 2 .. 64, what msk_elastic_field takes
+ELASTIC_MAX_ALPHA = 4096.0
 
 
-def gauss_taps(sigma) -> np.ndarray:
+def gauss_taps(sigma, max_sigma=GAUSS_MAX_SIGMA) -> np.ndarray:
     """The 2r+1 float32 weights of one blurred axis, r = int(4 sigma + 0.5) (scipy.ndimage.gaussian_filter's kernel at
     truncate 4, computed in float64 and rounded once); empty when r == 0.  The host path and the device path of the blur use
-    these same numbers."""
+    these same numbers; ``max_sigma`` is the limit of the kernel the taps are for (the elastic field's is ELASTIC_MAX_SIGMA)."""
     sigma = float(sigma)
-    if not 0.0 <= sigma <= GAUSS_MAX_SIGMA:
-        raise ValueError("sigma must be in [0, {}], got {}".format(GAUSS_MAX_SIGMA, sigma))
+    if not 0.0 <= sigma <= max_sigma:
+        raise ValueError("sigma must be in [0, {}], got {}".format(max_sigma, sigma))
     r = int(4.0 * sigma + 0.5)
     if r == 0:
         return np.zeros(0, np.float32)
     k = np.arange(-r, r + 1, dtype=np.float64)
     w = np.exp(-0.5 / (sigma * sigma) * k * k)
     return (w / w.sum()).astype(np.float32)
+
+
+def elastic_axes_mask(axes) -> int:
+    """bit a set for every source axis a of ``axes``, a subset of (0, 1, 2) without repeats"""
+    axes = [int(a) for a in axes]
+    if any(a not in (0, 1, 2) for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError("axes must be a subset of (0, 1, 2), got {}".format(axes))
+    return sum(1 << a for a in axes)
+
+
+def elastic_field_device(dev, roi, sigma, alpha, seed, axes=(0, 1, 2)) -> DeviceVolume:
+    """msk_elastic_field: the displacement field of an elastic deformation, alpha * (uniform counter noise smoothed by a
+    Gaussian of ``sigma`` in [0.5, 16] along W, H and D with zeros outside the patch), as a pooled float32 ``DeviceVolume`` of
+    shape ``(3,) + roi`` (``free()`` hands it back) for affine_patch_device's ``field``.  A component whose axis is not in
+    ``axes`` is zero.  The scratch volume comes from the pool and goes back to it.  Nothing is downloaded and nothing
+    synchronises."""
+    roi = tuple(int(r) for r in roi)
+    if len(roi) != 3:
+        raise ValueError("roi must have three extents, got {}".format(roi))
+    sigma, alpha = float(sigma), float(alpha)
+    if not ELASTIC_MIN_SIGMA <= sigma <= ELASTIC_MAX_SIGMA:
+        raise ValueError("sigma must be in [{}, {}], got {}".format(ELASTIC_MIN_SIGMA, ELASTIC_MAX_SIGMA, sigma))
+    taps = gauss_taps(sigma, ELASTIC_MAX_SIGMA)
+    mask = elastic_axes_mask(axes)
+    shape = (3,) + roi
+    with _pooled_outputs(dev, (shape, np.float32)) as (field,), _pooled_scratch(dev, int(np.prod(shape)) * 4) as tmp:
+        dev.call("msk_elastic_field", C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), *roi, taps.ctypes.data_as(C.c_void_p),
+                 (len(taps) - 1) // 2, C.c_float(alpha), mask, C.c_void_p(field.ptr), C.c_void_p(tmp))
+    return field
 
 
 def _float_volume(vol, what):

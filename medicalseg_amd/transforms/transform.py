@@ -830,14 +830,19 @@ def _affine_gather(vol, idx, outside):
     return np.where(ok, vol[tuple(clipped)], outside)
 
 
-def _affine_patch_host(img, label, origin, roi, m, pad, label_pad):
+def _affine_patch_host(img, label, origin, roi, m, pad, label_pad, field=None):
     """msk_affine_patch in numpy, float32 throughout, every operation rounded on its own: the grid of the patch, centred on
     origin + roi // 2, through the matrix; the image trilinearly (W, then H, then D; ``pad`` outside the volume), the label
-    at floor(p + 0.5) (``label_pad`` outside).  Equal to tests/affine_reference.py bit for bit."""
+    at floor(p + 0.5) (``label_pad`` outside).  Equal to tests/affine_reference.py bit for bit.  With ``field`` (float32
+    [3, rd, rh, rw], _elastic_field_host) the offsets are displaced before the matrix, msk_affine_patch_elastic: equal to
+    tests/elastic_reference.py bit for bit."""
     img = np.asarray(img, np.float32)
     m = np.asarray(m, np.float32).reshape(3, 3)
     oz, oy, ox = ((np.arange(r) - r // 2).astype(np.float32).reshape(sh)
                   for r, sh in zip(roi, ((-1, 1, 1), (1, -1, 1), (1, 1, -1))))
+    if field is not None:
+        field = np.asarray(field, np.float32)
+        oz, oy, ox = oz + field[0], oy + field[1], ox + field[2]
     p = [((m[a, 0] * oz + m[a, 1] * oy) + m[a, 2] * ox) + np.float32(int(origin[a]) + int(roi[a]) // 2) for a in range(3)]
     f = [np.floor(v) for v in p]
     t = [v - fl for v, fl in zip(p, f)]
@@ -923,6 +928,106 @@ class RandomAffinePatchCrop3D(RandomPatchCrop3D):
             return (_patch_crop_host(img, origin, self.size, self.pad_value),
                     None if label is None else _patch_crop_host(label, origin, self.size, self.label_pad))
         return _affine_patch_host(img, label, origin, self.size, m, self.pad_value, self.label_pad)
+
+
+# ---- elastic deformation of that patch (batchgenerators' SpatialTransform(do_elastic_deform=True); not in the reference) -----
+def _elastic_field_host(roi, sigma, alpha, seed, axes=(0, 1, 2)):
+    """msk_elastic_field in numpy, float32 throughout: [3, rd, rh, rw] = alpha * (counter noise in [-1, 1) smoothed along W, H
+    and D by gauss_taps(sigma) with zeros outside the patch; all 2r+1 terms of a line added in order, every multiply and add
+    rounded on its own).  A component whose axis is not in ``axes`` is zero.  Equal to tests/elastic_reference.py bit for bit."""
+    from ..preprocess import ELASTIC_MAX_SIGMA, gauss_taps
+    roi = tuple(int(r) for r in roi)
+    n = int(np.prod(roi))
+    w = gauss_taps(sigma, ELASTIC_MAX_SIGMA)
+    r = (len(w) - 1) // 2
+    with np.errstate(over="ignore"):
+        h = _splitmix64(_splitmix64(np.uint64(int(seed) & _MASK64)) + np.arange(3 * n, dtype=np.uint64))
+    x = ((h >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)).reshape((3,) + roi)
+    for a in range(3):
+        if a not in axes:
+            x[a] = 0.0
+    for axis in (3, 2, 1):
+        padding = [(0, 0)] * 4
+        padding[axis] = (r, r)
+        xp = np.moveaxis(np.pad(x, padding), axis, -1)
+        length = x.shape[axis]
+        acc = w[0] * xp[..., :length]
+        for k in range(1, 2 * r + 1):
+            acc = acc + w[k] * xp[..., k:k + length]
+        x = np.moveaxis(acc, -1, axis)
+    return np.ascontiguousarray(np.float32(alpha) * x)
+
+
+@manager.TRANSFORMS.add_component
+class RandomElasticAffinePatchCrop3D(RandomAffinePatchCrop3D):
+    """RandomAffinePatchCrop3D whose sampling grid is, with probability ``elastic_prob``, also deformed elastically --
+    batchgenerators' ``SpatialTransform(do_elastic_deform=True)``, MONAI's ``Rand3DElastic``: uniform noise per axis, smoothed
+    by a Gaussian of ``elastic_sigma`` voxels and scaled by ``elastic_alpha``, displaces the zero-centred grid before it is
+    rotated, scaled and moved to the chosen centre, and the volume is still read once.  The defaults are nnU-Net v1's.
+    ``elastic_axes``: the source axes that are displaced; ``(1, 2)`` keeps a thin slab from being displaced across slices.
+    Not in the reference.
+
+    Random stream: the parent's six draws and nine ``random.random()``, then always ``random.random()`` (the coin),
+    ``random.random()`` (alpha), ``random.random()`` (sigma) and ``random.getrandbits(64)`` (the seed of the counter noise),
+    whatever the coins and the data.  Without an elastic hit the call is the parent's: its select, then plain crops or
+    msk_affine_patch; neither elastic kernel is launched.  With an elastic hit and no matrix the identity matrix is used.  On
+    device volumes msk_patch_select, msk_elastic_field and msk_affine_patch_elastic run back to back: nothing is downloaded
+    and nothing synchronises."""
+
+    def __init__(self, size, num_classes, fg_prob=1. / 3., classes=None, pad_value=0, label_pad=0, rotate_prob=0.2, degrees=30,
+                 scale_prob=0.2, scale=(0.7, 1.4), per_axis_scale=False, elastic_prob=0.2, elastic_alpha=(0., 900.),
+                 elastic_sigma=(9., 13.), elastic_axes=(0, 1, 2)):
+        from ..preprocess import ELASTIC_MAX_ALPHA, ELASTIC_MAX_SIGMA, ELASTIC_MIN_SIGMA, elastic_axes_mask
+        super().__init__(size, num_classes, fg_prob, classes, pad_value, label_pad, rotate_prob, degrees, scale_prob, scale,
+                         per_axis_scale)
+        self.elastic_prob = _check_prob(elastic_prob)
+        self.elastic_alpha = _check_range(elastic_alpha, "elastic_alpha", lowest=0.0, highest=ELASTIC_MAX_ALPHA)
+        self.elastic_sigma = _check_range(elastic_sigma, "elastic_sigma", lowest=ELASTIC_MIN_SIGMA, highest=ELASTIC_MAX_SIGMA)
+        if not isinstance(elastic_axes, (tuple, list)):
+            raise ValueError("elastic_axes must be a subset of (0, 1, 2), got {}.".format(elastic_axes))
+        elastic_axes_mask(elastic_axes)
+        self.elastic_axes = tuple(sorted(int(a) for a in elastic_axes))
+        if 3 * self.size[0] * self.size[1] * self.size[2] >= 2 ** 31:
+            raise ValueError("the displacement field of a {} patch has 2^31 elements or more.".format(self.size))
+
+    def get_elastic(self):
+        """the four draws -> (alpha, sigma, seed), both float32 values, or None without a hit"""
+        coin, ua, us, seed = random.random(), random.random(), random.random(), random.getrandbits(64)
+        if not coin < self.elastic_prob:
+            return None
+        return float(np.float32(_value(self.elastic_alpha, ua))), float(np.float32(_value(self.elastic_sigma, us))), seed
+
+    def _device_elastic(self, img, label, sel, m, alpha, sigma, seed):
+        from ..preprocess import affine_patch_device, elastic_field_device
+        field = elastic_field_device(img.dev, self.size, sigma, alpha, seed, self.elastic_axes)
+        try:
+            if label is None:
+                return affine_patch_device(img, None, sel, self.size, m, self.pad_value, field=field), None
+            return affine_patch_device(img, label, sel, self.size, m, self.pad_value, self.label_pad, field=field)
+        finally:
+            field.free()                     # stream-ordered: the sampling kernel is enqueued in front of the next user
+
+    def __call__(self, img, label=None):
+        words = self.get_params(label is not None)
+        m = self.get_matrix()
+        hit = self.get_elastic()
+        if hit is None:                      # the parent's call from here on
+            if _on_device(img):
+                if m is None:
+                    return self._device_call(img, label, words, self._device_crops)
+                return self._device_call(img, label, words, lambda *a: self._device_affine(*a, m))
+            origin = self.select(img.shape[:3], label, words)[:3]
+            if m is None:
+                return (_patch_crop_host(img, origin, self.size, self.pad_value),
+                        None if label is None else _patch_crop_host(label, origin, self.size, self.label_pad))
+            return _affine_patch_host(img, label, origin, self.size, m, self.pad_value, self.label_pad)
+        if m is None:
+            m = np.eye(3, dtype=np.float32)
+        if _on_device(img):
+            return self._device_call(img, label, words, lambda *a: self._device_elastic(*a, m, *hit))
+        origin = self.select(img.shape[:3], label, words)[:3]
+        field = _elastic_field_host(self.size, hit[1], hit[0], hit[2], self.elastic_axes)
+        return _affine_patch_host(img, label, origin, self.size, m, self.pad_value, self.label_pad, field)
 
 
 @manager.TRANSFORMS.add_component
