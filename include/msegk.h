@@ -738,6 +738,46 @@ int msk_topk_ce_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int 
 int msk_topk_ce_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, const float* weights,
                     const void* workspace, const double* record, float coef, int accumulate, msk_tensor dz);
 
+/* ---- Lovasz-Softmax loss on an exact key-index radix sort (LovaszSoftmaxLoss, DiceLovaszLoss: Berman, Triki, Blaschko, CVPR
+ *      2018, PaddleSeg's LovaszSoftmaxLoss; the reference has no such loss, so every entry cites tests/lovasz_reference.py, the
+ *      statement) ---- */
+/* Bytes of workspace for `groups` groups of `voxels` voxels each (in [1, 2^31)) and `classes` classes (2 .. 64, groups x classes
+ * <= 65535): four planes of S = voxels rounded up to 64 words per (group, class), the histograms of a digit pass, 16 bytes per
+ * chunk of 4096 keys and plane.  Needs no context and no GPU.                                                                   */
+int msk_lovasz_workspace(long voxels, int classes, int groups, size_t* bytes);
+/* Lovasz-Softmax of logits [N,D,H,W,C] (ld >= C, 2 <= C <= 64) against int32 labels.  A group is the whole batch, or one sample
+ * when per_image != 0; its voxels are taken in raster order.  A voxel is valid when its label is in [0, C) and is not
+ * ignore_index; every other voxel takes no part.  Per (group g, class c) the plane p = g C + c: e_v = |[y_v == c] - p_vc| with p
+ * the float32 softmax (row maximum, expf, the sum in ascending class order, one division), sorted in descending order, ties in
+ * ascending voxel order; with G the plane's foreground voxels and cf_i those at sorted positions <= i,
+ * J_i = 1 - (G - cf_i) / (G + i + 1 - cf_i), g_i = J_i - J_{i-1} (J_{-1} = 0) in float64 from exact integers, and
+ * L = sum_i float64(e_(i)) g_i in the FIXED order of msk_intensity_stats over the sorted positions.  A class counts in its group
+ * when G > 0 (class_mode 0), always (1: a class with G = 0 has g_0 = 1 and nothing else), or when G > 0 and its bit is set in
+ * class_mask (2).  loss = the mean over the groups of the mean of L over the group's counted classes (0 for a group without one).
+ * out (DEVICE, 2 + C floats) = {loss, counted (group, class) pairs, per class the mean L over the groups that count it}.
+ * stats (DEVICE, 4 groups C + 2 doubles, 8-byte aligned) = per plane {n_valid, G, L, scale = 1 / (groups x counted classes of
+ * the group), 0 for a class that does not count}, then {loss, pairs}; every field is exact and reproducible.  workspace (DEVICE,
+ * 16-byte aligned, at least msk_lovasz_workspace(voxels of a group, C, groups) bytes, overlapping no operand) holds afterwards,
+ * in planes of S words each starting on a 256-byte boundary: the sorted keys of all planes (bits 0-29: 0x3f800000 - the bits of
+ * e, ascending; bit 31: [y == c]; 0x3fffffff: a voxel that takes no part, behind all valid ones), then their voxel indices inside
+ * the group (the permutation), then the float32 planes dL/de_v = float32(g_rank(v) scale), 0 at a voxel that takes no part.
+ * 22 launches on the context stream: the pack, four digit passes of 8, 8, 8 and 6 bits (histogram, two scan kernels, stable
+ * scatter of key and index), the foreground prefix, the sums, the finish.  Integer atomics in LDS histograms only, no float
+ * atomics, no synchronisation, no download.  With several ranks the sort is that of the calling rank.                            */
+int msk_lovasz_fwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, int class_mode,
+                   unsigned long long class_mask, int per_image, void* workspace, size_t workspace_bytes, float* out,
+                   double* stats);
+/* dz_k (+)= coef p_k (s_k ge_k - sum_c s_c ge_c p_c) with ge = the dL/de planes the forward call left in the workspace, p the
+ * softmax recomputed, s_c = -1 where y == c and +1 elsewhere; evaluated as p_k ((a_k - a_m) + sum_c p_c (a_m - a_c)) with
+ * a = s ge and m the class of the largest probability, which does not cancel where the softmax is nearly one-hot.  A voxel that
+ * takes no part gets zeros; when accumulate != 0 adds into dz its value stays (a lane's own form skips it, the LDS-tile forms add
+ * +0.0 to it, which turns a stored -0.0 into +0.0).  stats is the record of the forward call (it travels with the workspace; the
+ * pass reads the planes only).  One launch.  Argument errors of all three, reported before any launch: null or misaligned
+ * pointers, C outside 2..64, a group of 2^31 voxels or more, a workspace that is too small or overlaps an operand, a class_mode
+ * outside 0..2, a class_mask that is empty or names a class outside [0, C), a dz of another shape.                               */
+int msk_lovasz_bwd(msk_ctx* ctx, msk_tensor logits, const int32_t* labels, int ignore_index, int per_image,
+                   const void* workspace, size_t workspace_bytes, const double* stats, float coef, int accumulate, msk_tensor dz);
+
 /* ---- boundary loss on signed distance maps built on the device (BoundaryLoss, DiceBoundaryLoss: Kervadec et al., MIDL 2019,
  *      the BDLoss / DC_and_BD_loss of the nnU-Net loss collections; the reference has no such loss, so every entry cites
  *      tests/boundary_reference.py, the statement) ---- */

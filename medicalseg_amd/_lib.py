@@ -164,6 +164,9 @@ SIGNATURES = {
     "msk_topk_select": (_i, [_vp, _vp, C.c_long, C.c_long, _vp, _vp]),
     "msk_topk_ce_fwd": (_i, [_vp, _T, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     "msk_topk_ce_bwd": (_i, [_vp, _T, _vp, _i, _vp, _vp, _vp, _f, _i, _T]),
+    "msk_lovasz_workspace": (_i, [C.c_long, _i, _i, C.POINTER(_sz)]),
+    "msk_lovasz_fwd": (_i, [_vp, _T, _vp, _i, _i, _u64, _i, _vp, _sz, _vp, _vp]),
+    "msk_lovasz_bwd": (_i, [_vp, _T, _vp, _i, _i, _vp, _sz, _vp, _f, _i, _T]),
     "msk_fg_stats_workspace": (_i, [C.c_long, C.POINTER(_sz)]),
     "msk_fg_stats": (_i, [_vp, _vp, _vp, C.c_long, _i, _d, _d, _vp, _vp]),
     "msk_clip_zscore": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp, _i, _f, _vp]),

@@ -7,3 +7,4 @@ from .region_losses import DiceCELoss, FocalLoss, SoftDiceLoss, TverskyLoss
 from .region_based_losses import DiceBCERegionLoss, RegionSpec
 from .topk_losses import DiceTopKLoss, TopKLoss
 from .boundary_losses import BoundaryLoss, DiceBoundaryLoss
+from .lovasz_losses import DiceLovaszLoss, LovaszSoftmaxLoss

@@ -266,6 +266,45 @@ class TopKNode(Node):
                       accumulate, dz.msk())
 
 
+LOVASZ_PRESENT, LOVASZ_ALL, LOVASZ_LIST = 0, 1, 2
+
+
+class LovaszNode(Node):
+    """Lovasz-Softmax (the 'lovasz' term, out[0]; out[1] is the number of counted (group, class) pairs, out[2:] the per-class
+    means): msk_lovasz_fwd / msk_lovasz_bwd.  `settings` is (ignore_index, class_mode, class_mask, per_image): class_mode one of
+    LOVASZ_PRESENT / LOVASZ_ALL / LOVASZ_LIST, class_mask the bits of the listed classes.  The workspace (the sorted keys, the
+    permutation and the dL/de planes the backward pass reads) and the record come from the activation arena: they live until the
+    next model forward, like the other records.  With several ranks the sort is that of this rank's batch."""
+    SLOTS = {"lovasz": 0}
+
+    def __init__(self, logits: Tensor, labels: IntTensor, settings):
+        super().__init__(logits, labels)
+        self.ignore_index, self.class_mode, self.class_mask, self.per_image = settings
+        self.groups = logits.n if self.per_image else 1
+        self.ws_ptr = None
+        self.ws_bytes = 0
+
+    def stats_doubles(self):
+        return 4 * self.groups * self.C + 2
+
+    def _args(self):
+        return (self.logits.msk(), C.c_void_p(self.labels.ptr), int(self.ignore_index))
+
+    def _forward(self):
+        if self.ws_ptr is None:
+            nbytes = C.c_size_t(0)
+            voxels = self.logits.n * self.logits.d * self.logits.h * self.logits.w // self.groups
+            if self.dev.lib.msk_lovasz_workspace(C.c_long(voxels), self.C, self.groups, C.byref(nbytes)) != 0:
+                raise ValueError("msk_lovasz_workspace refused %d groups of %d voxels and %d classes" % (self.groups, voxels, self.C))
+            self.ws_ptr, self.ws_bytes = self.dev.arena.alloc(nbytes.value), nbytes.value
+        self.dev.call("msk_lovasz_fwd", *self._args(), int(self.class_mode), C.c_uint64(self.class_mask), int(self.per_image),
+                      C.c_void_p(self.ws_ptr), C.c_size_t(self.ws_bytes), C.c_void_p(self.out_ptr), C.c_void_p(self.stats_ptr))
+
+    def _backward(self, coef, _, accumulate, dz):
+        self.dev.call("msk_lovasz_bwd", *self._args(), int(self.per_image), C.c_void_p(self.ws_ptr), C.c_size_t(self.ws_bytes),
+                      C.c_void_p(self.stats_ptr), C.c_float(coef), accumulate, dz.msk())
+
+
 class BoundaryNode(Node):
     """Boundary loss (the 'boundary' term, out[0]; out[1] is the mean of the absolute terms, out[2:] the per-class means):
     msk_label_sdf, then msk_boundary_loss_fwd / msk_boundary_loss_bwd.  `settings` is (ignore_index, class_mask, spacing):
@@ -327,7 +366,7 @@ def node_for(kind, logits: Tensor, labels, settings=()):
 
 
 class Scalar:
-    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce' | 'topk' | 'boundary'): the float node.slot(which) of the node's
+    """A scalar loss = sum_i coef_i * term_i, term = (node, 'ce' | 'dice' | 'bce' | 'topk' | 'boundary' | 'lovasz'): the float node.slot(which) of the node's
     record.  Values stay on the device until ``numpy()``/``float()`` (one sync), so the train loop can defer host
     syncs to log boundaries."""
 

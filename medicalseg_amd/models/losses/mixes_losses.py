@@ -2,7 +2,8 @@ from ... import nn
 from ...cvlibs import manager
 
 # the members that return (loss, per_channel_dice)
-_DICE_LOSSES = ("DiceLoss", "SoftDiceLoss", "TverskyLoss", "DiceCELoss", "DiceTopKLoss", "DiceBoundaryLoss", "DiceBCERegionLoss")
+_DICE_LOSSES = ("DiceLoss", "SoftDiceLoss", "TverskyLoss", "DiceCELoss", "DiceTopKLoss", "DiceBoundaryLoss", "DiceBCERegionLoss",
+                "DiceLovaszLoss")
 
 
 @manager.LOSSES.add_component
@@ -11,7 +12,7 @@ class MixedLoss(nn.Layer):
 
     forward returns ``(loss_list, per_channel_dice)``: the weighted terms stay separate so that
     the train loop can log them individually; a member whose class is NAMED ``DiceLoss`` (or
-    ``SoftDiceLoss``, ``TverskyLoss``, ``DiceCELoss``, ``DiceTopKLoss``, ``DiceBoundaryLoss``, ``DiceBCERegionLoss``) also returns its per-class dice, which is
+    ``SoftDiceLoss``, ``TverskyLoss``, ``DiceCELoss``, ``DiceTopKLoss``, ``DiceBoundaryLoss``, ``DiceBCERegionLoss``, ``DiceLovaszLoss``) also returns its per-class dice, which is
     passed through (the reference dispatches on the class name too, :57).  Here every term is a device-side ``Scalar`` of the fused loss node."""
 
     def __init__(self, losses, coef):

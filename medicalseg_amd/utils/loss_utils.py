@@ -7,7 +7,7 @@ from ..device import Tensor
 
 _EDGE_LOSSES = ('BCELoss', 'FocalLoss')
 _DICE_LOSSES = ('DiceLoss', 'SoftDiceLoss', 'TverskyLoss', 'DiceCELoss', 'DiceTopKLoss', 'DiceBoundaryLoss',
-                'DiceBCERegionLoss')   # they return (loss, per_channel_dice)
+                'DiceBCERegionLoss', 'DiceLovaszLoss')   # they return (loss, per_channel_dice)
 
 
 def check_logits_losses(logits_list, losses):
